@@ -1,7 +1,14 @@
 """Benchmark: FiBiNET training samples/s on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--deterministic] [--full]
   N > 1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run does what the headline figure needs and nothing else: it sets up, primes and warms up,
+picks the launch mode (--mode auto), times the K steps, writes the last timed step's outputs
+(--dump-outputs) and prints the line with the contract keys.  --full adds every other measurement
+to the line: the rooflines, the fp32 and bf16_fwd lines, the inference leg, the CPU baselines and,
+at N > 1, the other BatchNorm mode and the other collective path (the --no-* options take legs
+out of a --full run).
 
 Workload (DESIGN.md "Benchmark"): config C3 of BASELINE.json -- FiBiNET emb_dim=128 with the
 item_emb_d128 dense feature, batch 8192 per GPU, history 20, bf16 GEMM operands / fp32
@@ -10,7 +17,23 @@ OneCycleLR), synthetic MicroLens-shaped batches resident in HBM.  Item vocabular
 per GPU, row-sharded (N = 8 -> the 10 M rows of config C4).  Weak scaling: per-GPU batch and
 per-GPU table shard are fixed as N grows.
 
-One JSON line on rank 0 with the contract keys plus
+--dump-outputs DIR: after the timed steps, what the last one left with its caller, as float32 /
+float64 DIR/<name>.npy: loss (the step's return value), every dense parameter and buffer under its
+state_dict key, and item_emb.weight.sample = a fixed seeded sample of DUMP_TABLE_ROWS table rows
+(item_emb.weight.rows holds their indices), brought up to the current step as state_dict() does.
+24.9 MB in all at C3.  The timed steps are the trainer's default step whatever else is asked for, so
+value and ms_per_step mean the same with and without --dump-outputs.  That step folds rows named
+several times in a batch with float atomics, whose arrival order changes the last bit and, through
+Adam, the whole trajectory within a few thousand steps (three 3000-step runs ended at losses 0.403 /
+0.359 / 0.320): its own final state cannot be compared between runs.  So the files are written by a
+second, untimed pass over the same seeded inputs, schedule and number of steps in deterministic mode
+(the fixed-point, order-independent fold; everything else is the same code): two runs with the same
+arguments write the same bits and two builds compare file by file.  It costs one more set-up plus
+(priming + W + K) untimed steps.  --deterministic times that mode itself (~4 % more per step at C3);
+the files then come from the timed steps and there is no second pass.  The line says which
+("duplicate_fold", "outputs").
+
+One JSON line on rank 0 with the contract keys plus (--full)
   roofline:      the dominant kernel of the step (largest average launch time among the probed
                  ones), its launches timed by their own start / end events inside an eager probe
                  pass (the library launches every kernel with hipExtLaunchKernelGGL; armed per call
@@ -56,6 +79,19 @@ def parse():
     ap.add_argument("--steps", type=int, default=30)
     # untimed warm-up steps; bench tops them up to 2F steps of priming (steady-state lazy Adam)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement beside the headline: rooflines (probe passes), the fp32 and bf16_fwd "
+                         "lines, the inference leg, the CPU baselines; N > 1: the other BatchNorm mode and the "
+                         "other collective path.  Off: the line holds the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left with its caller (loss, dense parameters and buffers, "
+                         "a seeded sample of table rows) as DIR/<name>.npy.  The timed steps keep the default "
+                         "float-atomic duplicate fold, whose state is not reproducible run to run, so the files come "
+                         "from a second, untimed pass over the same steps in deterministic mode (with "
+                         "--deterministic: from the timed steps themselves)")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="time the trainer in deterministic mode (fixed-point duplicate fold on the main stream, "
+                         "~4 %% more per step at C3); never implied by another option")
     ap.add_argument("--batch", type=int, default=8192, help="per-GPU batch")
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--rows-per-gpu", type=int, default=ROWS_PER_GPU)
@@ -100,7 +136,13 @@ def parse():
                     help="N > 1: skip the second measurement in the other BatchNorm mode")
     ap.add_argument("--no-fp32", dest="also_fp32", action="store_false",
                     help="skip the fp32 and bf16_fwd C3 measurements embedded in the line")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run: the headline only (the step count behind the LR schedule stays the --full run's,
+        # so both compute the same steps)
+        args.also_fp32 = args.inference = args.cpu_plan = args.live_probes = False
+        args.no_cpu_baseline = args.no_other_bn = True
+    return args
 
 
 def gather_bytes_per_sample(d: int, L: int = 20) -> int:
@@ -397,9 +439,44 @@ def native_ab(args, world, rank, dev):
     return out
 
 
-def measure(args, dtype, world, rank, dev, rehearsal, backend, bn=None, native=None):
+DUMP_TABLE_ROWS = 16384      # --dump-outputs: seeded sample of this rank's table rows
+
+
+def dump_outputs(tr, dump_dir: str, rank: int) -> None:
+    """--dump-outputs: what the last timed step left with its caller -- the loss it returned and the
+    state it updated: every dense parameter and buffer under its state_dict key and a fixed seeded
+    sample of the item table's rows, brought up to the current step first (the lazy table Adam's
+    flush, as state_dict() and predict() do).  float32 (integer buffers and the row indices: float64)
+    .npy files, 24.9 MB in all at C3; rank 0 writes (N > 1: its own row block's sample)."""
+    import numpy as np
+    from ctr_recommendation_amd.trainer import TABLE
+    tr.flush()
+    torch.cuda.synchronize()
+    if rank != 0:
+        return
+    os.makedirs(dump_dir, exist_ok=True)
+
+    def save(name, t):
+        t = t.detach().to(torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64)
+        np.save(os.path.join(dump_dir, name + ".npy"), t.cpu().numpy())
+
+    save("loss", tr.loss)
+    for k in tr.key_order:
+        if k != TABLE:
+            save(k, tr.p[k])
+    g = torch.Generator()
+    g.manual_seed(2025)
+    rows = torch.randperm(tr.rows_local, generator=g)[:DUMP_TABLE_ROWS].sort().values
+    save(TABLE + ".rows", rows)
+    save(TABLE + ".sample", tr.E[rows.to(tr.E.device)])
+
+
+def measure(args, dtype, world, rank, dev, rehearsal, backend, bn=None, native=None, dump_dir=None,
+            deterministic=None):
     """Build a trainer for `dtype`, bring it to steady state, time K steps; returns the result dict.
-    native (N > 1): True / False = native RCCL + step programs / torch.distributed (None: FBN_NATIVE_COMM)."""
+    native (N > 1): True / False = native RCCL + step programs / torch.distributed (None: FBN_NATIVE_COMM).
+    dump_dir: --dump-outputs of the last timed step; deterministic: the trainer's mode (None: its default,
+    the float-atomic duplicate fold unless FBN_DETERMINISTIC=1)."""
     from ctr_recommendation_amd.data import make_device_batches
     from ctr_recommendation_amd import ops
     from ctr_recommendation_amd.trainer import FiBiNETTrainer
@@ -438,6 +515,7 @@ def measure(args, dtype, world, rank, dev, rehearsal, backend, bn=None, native=N
     tr = FiBiNETTrainer(cfg, total_steps=total, batch_size=B, device=dev, rank=rank, world=world,
                         init_state=init, stage_on_cpu=rehearsal, lazy_window=F, prefetch_rows=args.prefetch,
                         table_adam=args.table_adam,
+                        deterministic=deterministic,
                         shard=sharded, sync_bn=(bn or args.bn) == "sync", native_comm=native)
     del init
     batches = make_device_batches(nb, B, V, L, dev, seed=2025 + rank, zipf=args.zipf)
@@ -520,6 +598,7 @@ def measure(args, dtype, world, rank, dev, rehearsal, backend, bn=None, native=N
     torch.cuda.synchronize()
     if tr.xchg is not None:
         tr.xchg.host_wait_s = 0.0
+    step0 = tr.device_step()                      # the device's optimizer-step counter (4-byte read, GPU idle)
     t0 = time.perf_counter()
     i_timed = i
     for _ in range(K):
@@ -537,6 +616,19 @@ def measure(args, dtype, world, rank, dev, rehearsal, backend, bn=None, native=N
         dt = float(tt.item())
     tr.check_ids()                                # ids in range, no step past total_steps
     loss = float(tr.loss.item())
+    counted = tr.device_step() - step0            # steps the device took inside the timed region
+    out = {"dt": dt, "t_host": t_host, "t_wait": t_wait, "K": K, "counted": counted, "W": W, "B": B, "L": L, "V": V, "d": d,
+           "rows_local": tr.rows_local, "loss": loss, "table_adam": tr.table_adam,
+           "deterministic": tr.deterministic, "graphs": mode_now[0] == "graph", "launch_mode": mode_now[0],
+           "collectives": (None if not sharded else "RCCL on the step's stream (csrc/comm.cpp)"
+                           if tr.native_comm is not None else "torch.distributed process group"),
+           "mode_trial_ms_per_step": {k: [round(x, 4) for x in v] for k, v in trial.items()} if trial else None,
+           "prime": prime, "batches": nb}
+    if not args.full:
+        # a plain run ends here: the headline and, when asked for, the last timed step's outputs
+        if dump_dir:
+            dump_outputs(tr, dump_dir, rank)
+        return out
 
     # ---- replay length of the claimed rows at this point of steady state (mean steps per row)
     b_next = batches[i % nb][0]
@@ -551,6 +643,9 @@ def measure(args, dtype, world, rank, dev, rehearsal, backend, bn=None, native=N
     # N > 1 (and the one-rank sharded run): the owner catches the next step's requested rows up
     # ahead (fbn_adam_prefetch_rows), so the claimed-row catch-up replays only the stale ones too
     owner_pf = bool(getattr(tr, "prefetch_owner", False)) and tr.xchg is not None
+    if dump_dir:
+        # (the probe passes below then start from a flushed table: shorter replays in their catch-up)
+        dump_outputs(tr, dump_dir, rank)
 
     # ---- probe pass: eager steps with the dominant kernels' spans probed (_lib.KernelProbe)
     probe = {}
@@ -683,15 +778,10 @@ def measure(args, dtype, world, rank, dev, rehearsal, backend, bn=None, native=N
             24 * tr.rows_local * d + 4 * tr.rows_local, "GB/s", HBM_PEAK_GBS, "hbm", "24 B x rows x d + 4 B x rows")
     main_k = [r for r in rooflines if "side stream" not in r["kernel"] and " alone " not in r["kernel"]]
     dominant = max(main_k, key=lambda r: r["avg_launch_ms"]) if main_k else None
-    out = {"dt": dt, "t_host": t_host, "t_wait": t_wait, "K": K, "W": W, "B": B, "L": L, "V": V, "d": d, "rows_local": tr.rows_local, "loss": loss,
-           "rooflines": rooflines, "roofline": dominant, "table_adam": tr.table_adam,
-           "graphs": mode_now[0] == "graph", "launch_mode": mode_now[0],
-           "probe_source": ("the timed step-program replays (kernel-span probes recorded into the programs)"
-                            if timed_src else "eager probe steps after the timed region"),
-           "collectives": (None if not sharded else "RCCL on the step's stream (csrc/comm.cpp)"
-                           if tr.native_comm is not None else "torch.distributed process group"),
-           "mode_trial_ms_per_step": {k: [round(x, 4) for x in v] for k, v in trial.items()} if trial else None,
-           "prime": prime, "batches": nb, "lag": lag, "stale": stale, "touched": touched, "prefetch": prefetch}
+    out.update({"rooflines": rooflines, "roofline": dominant,
+                "probe_source": ("the timed step-program replays (kernel-span probes recorded into the programs)"
+                                 if timed_src else "eager probe steps after the timed region"),
+                "lag": lag, "stale": stale, "touched": touched, "prefetch": prefetch})
     del graphs, progs, tr, batches
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
@@ -738,10 +828,10 @@ def _child_line(dtype: str):
         if skip:
             skip = False
             continue
-        if x == "--dtype":
+        if x in ("--dtype", "--dump-outputs"):     # (the outputs are the headline's, written by the parent)
             skip = True
             continue
-        if not x.startswith("--dtype="):
+        if not x.startswith(("--dtype=", "--dump-outputs=")):
             argv.append(x)
     cmd = [sys.executable, os.path.abspath(__file__)] + argv + [
         "--dtype", dtype, "--no-fp32", "--no-cpu-baseline", "--no-cpu-plan", "--no-inference"]
@@ -786,6 +876,10 @@ def main():
     # A/B, deterministic, bitwise) before timing it; the headline runs the validated path, the other
     # one is timed beside it.  FBN_BENCH_AB=0 skips the A/B (FBN_NATIVE_COMM then decides)
     ab, native, torch_line, native_err = None, None, None, None
+    # the timed pass runs the trainer's default step unless --deterministic asks for the other fold; only
+    # then are its own outputs the same run after run, and only then does it write them itself
+    det = True if args.deterministic else None
+    dump1 = args.dump_outputs if args.deterministic else None
     if (world > 1 or FORCE_SHARD) and not rehearsal and os.environ.get("FBN_BENCH_AB", "1") != "0":
         ab = native_ab(args, world, rank, dev)
         native = bool(ab["use_native"])
@@ -794,7 +888,8 @@ def main():
             print(f"[bench] native-RCCL A/B: {json.dumps(ab)}", file=sys.stderr, flush=True)
     if native:
         try:
-            r = measure(args, args.dtype, world, rank, dev, rehearsal, backend, native=True)
+            r = measure(args, args.dtype, world, rank, dev, rehearsal, backend, native=True,
+                        dump_dir=dump1, deterministic=det)
             ok = True
         except Exception as e:       # a watchdog abort mid-run: every rank falls back together
             ok, native_err = False, f"{type(e).__name__}: {e}"[:400]
@@ -802,13 +897,28 @@ def main():
         ok_all, _ = _ab_agree(ok, -1, dev)
         _release()
         if ok_all and ab.get("torch") is not None:      # (the torch path ran in the A/B)
-            torch_line = measure(args, args.dtype, world, rank, dev, rehearsal, backend, native=False)
+            if args.full:
+                torch_line = measure(args, args.dtype, world, rank, dev, rehearsal, backend, native=False,
+                                     deterministic=det)
         else:
             native = False
-            r = measure(args, args.dtype, world, rank, dev, rehearsal, backend, native=False)
+            r = measure(args, args.dtype, world, rank, dev, rehearsal, backend, native=False,
+                        dump_dir=dump1, deterministic=det)
     else:
         r = measure(args, args.dtype, world, rank, dev, rehearsal, backend,
-                    native=None if ab is None else False)
+                    native=None if ab is None else False, dump_dir=dump1, deterministic=det)
+    outs = None
+    if args.dump_outputs and dump1 is None:
+        # the outputs pass: the same arguments, batches, schedule and number of steps once more, untimed, in
+        # deterministic mode.  The timed pass's float-atomic duplicate fold differs in the last bit from run
+        # to run and Adam amplifies that: three runs of 3000 steps ended at losses 0.403 /
+        # 0.359 / 0.320, so its own state cannot be compared between runs or builds; this pass's can, bit
+        # for bit.  The headline above is untouched by it
+        _release()
+        plain = argparse.Namespace(**{**vars(args), "full": False, "live_probes": False})
+        outs = measure(plain, args.dtype, world, rank, dev, rehearsal, backend,
+                       native=None if ab is None else bool(native), dump_dir=args.dump_outputs, deterministic=True)
+        _release()
     alt = alt16 = None
     if args.also_fp32 and args.dtype == "bf16" and world == 1:
         # each in a process of its own (_child_line), the headline's state released first
@@ -825,7 +935,7 @@ def main():
         # both BatchNorm modes at N > 1: the other one as an embedded line (SyncBN = the parity mode)
         _release()
         other_bn = measure(args, args.dtype, world, rank, dev, rehearsal, backend,
-                           bn="sync" if args.bn == "local" else "local", native=native)
+                           bn="sync" if args.bn == "local" else "local", native=native, deterministic=det)
 
     if rank == 0:
         K, B, dt = r["K"], r["B"], r["dt"]
@@ -835,7 +945,9 @@ def main():
             "unit": "samples/s",
             "n_gpus": world,
             "steps": K,
+            "timed_steps_counted": r["counted"],       # the device's step counter over the timed region
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(dt / K * 1e3, 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -860,20 +972,28 @@ def main():
             "host_enqueue_ms_per_step": round(r["t_host"] / K * 1e3, 4),
             **({"host_wait_ms_per_step": round(r["t_wait"] / K * 1e3, 4),
                 "host_busy_ms_per_step": round((r["t_host"] - r["t_wait"]) / K * 1e3, 4)} if r["t_wait"] else {}),
-            "roofline": r["roofline"],
-            "rooflines": r["rooflines"],
-            "rooflines_in_step_from": r["probe_source"],
+            **({"roofline": r["roofline"], "rooflines": r["rooflines"],
+                "rooflines_in_step_from": r["probe_source"]} if args.full else {}),
             "table_adam": r["table_adam"],
+            "duplicate_fold": ("fixed point, order-independent (--deterministic: bitwise reproducible run to run)"
+                               if r["deterministic"] else "float atomics (the default)"),
+            **({"outputs": {"from": ("the timed steps themselves" if outs is None else
+                                     "a second, untimed pass over the same steps in deterministic mode (the timed "
+                                     "pass's float-atomic fold is not reproducible run to run)"),
+                            "final_loss": round((outs or r)["loss"], 5),
+                            "steps_counted": (outs or r)["counted"]}} if args.dump_outputs else {}),
             "steady_state": {"priming_steps": r["prime"], "warmup_steps": args.warmup,
-                             "mean_replay_steps_per_claimed_row": round(r["lag"], 2),
-                             "rows_touched_next_step": r["touched"],
-                             "rows_replayed_on_critical_path": r["stale"],
-                             "next_batch_prefetch": r["prefetch"],
+                             **({"mean_replay_steps_per_claimed_row": round(r["lag"], 2),
+                                 "rows_touched_next_step": r["touched"],
+                                 "rows_replayed_on_critical_path": r["stale"],
+                                 "next_batch_prefetch": r["prefetch"]} if args.full else {}),
                              "note": "untimed priming tops the warm-up up to 2F = 256 steps so the lazy "
-                                     "table Adam is at steady state whatever --warmup is; with the next-batch "
-                                     "prefetch the rows of step t+1 that step t does not touch are replayed on "
-                                     "the side stream during step t (exact), so the claimed-row catch-up on the "
-                                     "critical path replays only rows_replayed_on_critical_path rows"},
+                                     "table Adam is at steady state whatever --warmup is"
+                                     + ("; with the next-batch "
+                                        "prefetch the rows of step t+1 that step t does not touch are replayed on "
+                                        "the side stream during step t (exact), so the claimed-row catch-up on the "
+                                        "critical path replays only rows_replayed_on_critical_path rows"
+                                        if args.full else "")},
             "final_loss": round(r["loss"], 5),
         }
         if alt is not None:

@@ -6,7 +6,7 @@ N=$1; shift
 mkdir -p $R/gpurun_out
 for i in $(seq 1 $N); do
   for e in "$@"; do
-    (export BENCH_ARGS= $e; timeout -k 10 300 python $R/bench.py --no-cpu-baseline --no-fp32 --no-inference $BENCH_ARGS \
+    (export BENCH_ARGS= $e; timeout -k 10 300 python $R/bench.py --full --no-cpu-baseline --no-fp32 --no-inference $BENCH_ARGS \
        > $R/gpurun_out/abarm.json 2>/dev/null) || exit 1
     echo "arm [$e] round $i $(python -c "
 import json; d=json.loads(open('$R/gpurun_out/abarm.json').read().splitlines()[-1])

@@ -7,7 +7,7 @@ ARGS=$1; shift
 mkdir -p $R/gpurun_out
 for i in $(seq 1 $N); do
   for e in "$@"; do
-    (export FBN_AB_ARM=1 $e; timeout -k 10 300 python $R/bench.py --no-cpu-baseline --no-fp32 --no-inference $ARGS \
+    (export FBN_AB_ARM=1 $e; timeout -k 10 300 python $R/bench.py --full --no-cpu-baseline --no-fp32 --no-inference $ARGS \
        > $R/gpurun_out/abarm.json 2>/dev/null) || exit 1
     echo "arm [$e] round $i $(python -c "
 import json; d=json.loads(open('$R/gpurun_out/abarm.json').read().splitlines()[-1])

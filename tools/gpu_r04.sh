@@ -12,5 +12,5 @@ timeout -k 10 900 python -u -m pytest -v --timeout 800 --timeout-method thread \
 rc=$?
 echo "tests rc=$rc"; tail -3 $OUT/tests.log
 [ $rc -le 1 ] || exit $rc
-timeout -k 10 420 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 420 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 rc2=$?; echo "bench rc=$rc2"; exit $(( rc2 != 0 ? rc2 : rc ))

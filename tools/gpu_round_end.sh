@@ -10,11 +10,11 @@ mkdir -p $OUT
 bash $R/tools/gpu_final.sh $TAG || exit $?
 for bn in local sync; do
   FBN_BENCH_SHARD=1 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 \
-    timeout -k 10 300 python $R/bench.py --gpus 1 --no-fp32 --no-cpu-baseline --bn $bn > $OUT/shard_${bn}_$TAG.json \
+    timeout -k 10 300 python $R/bench.py --gpus 1 --bn $bn > $OUT/shard_${bn}_$TAG.json \
     2>/dev/null || exit 1
   echo "shard bn=$bn $(grep -o '"ms_per_step": [0-9.]*' $OUT/shard_${bn}_$TAG.json)"
 done
 FBN_BENCH_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 \
-  --master-addr 127.0.0.1 --master-port 29541 $R/bench.py --gpus 4 --no-fp32 --steps 5 --warmup 2 --prime 0 \
+  --master-addr 127.0.0.1 --master-port 29541 $R/bench.py --gpus 4 --steps 5 --warmup 2 --prime 0 \
   --batches 8 --rows-per-gpu 200000 > $OUT/rehearse4_$TAG.json 2> $OUT/rehearse4_$TAG.err
 rc=$?; echo "rehearsal (4 ranks, gloo) rc=$rc"; exit $rc

@@ -45,15 +45,15 @@ for step in "$@"; do
       grep -E "^(hip|f64|fp32)" $O/bisect.log || true ;;
     step1) timeout -k 10 300 python -m tests.parity_bisect step1 --out $O/step1.json > $O/step1.log 2>&1; rc=$?
            tail -5 $O/step1.log ;;
-    bench) timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err; rc=$?; cat $O/bench.json | head -c 600; echo ;;
-    benchq) timeout -k 10 400 python bench.py --no-cpu-baseline --no-cpu-plan --no-inference --no-fp32 \
+    bench) timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err; rc=$?; cat $O/bench.json | head -c 600; echo ;;
+    benchq) timeout -k 10 400 python bench.py --full --no-cpu-baseline --no-cpu-plan --no-inference --no-fp32 \
               > $O/benchq.json 2> $O/benchq.err; rc=$?; head -c 400 $O/benchq.json; echo ;;
-    zipf) timeout -k 10 400 python bench.py --zipf 1.05 --no-cpu-baseline --no-cpu-plan --no-inference --no-fp32 \
+    zipf) timeout -k 10 400 python bench.py --full --zipf 1.05 --no-cpu-baseline --no-cpu-plan --no-inference --no-fp32 \
             > $O/zipf.json 2> $O/zipf.err; rc=$?; head -c 400 $O/zipf.json; echo ;;
-    c2) timeout -k 10 400 python bench.py --dim 16 --batch 4096 --rows-per-gpu 1000000 --no-cpu-baseline --no-cpu-plan \
+    c2) timeout -k 10 400 python bench.py --full --dim 16 --batch 4096 --rows-per-gpu 1000000 --no-cpu-baseline --no-cpu-plan \
           --no-inference --no-fp32 > $O/c2.json 2> $O/c2.err; rc=$?; head -c 400 $O/c2.json; echo ;;
     shard) FBN_BENCH_SHARD=1 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 \
-             timeout -k 10 300 python bench.py --gpus 1 --no-fp32 --no-cpu-baseline --no-cpu-plan --no-inference \
+             timeout -k 10 300 python bench.py --full --gpus 1 --no-fp32 --no-cpu-baseline --no-cpu-plan --no-inference \
              --bn local > $O/shard.json 2> $O/shard.err; rc=$?; head -c 400 $O/shard.json; echo ;;
     gather) { timeout -k 10 300 python tools/time_fields.py "plain5:" "plain10:FBN_FIELDS_HCH=10" \
                 "plain20:FBN_FIELDS_HCH=20" "cmp5:FBN_FIELDS_CMP=1" "cmp8:FBN_FIELDS_CMP=1,FBN_FIELDS_HCH=8" \
@@ -65,7 +65,7 @@ for step in "$@"; do
             "noitem:FBN_FIELDS_ABL=4" "stores_only:FBN_FIELDS_ABL=5" "hist_only:FBN_FIELDS_ABL=6" "none:FBN_FIELDS_ABL=7" \
             > $O/gabl.txt 2>&1; rc=$?; grep -v Warn $O/gabl.txt ;;
     prof) (cd /tmp && export TMPDIR=/tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv \
-             -d $O/prof -o run -- python $R/bench.py --no-cpu-baseline --no-cpu-plan --no-inference --no-fp32 \
+             -d $O/prof -o run -- python $R/bench.py --full --no-cpu-baseline --no-cpu-plan --no-inference --no-fp32 \
              > $O/prof.log 2>&1); rc=$?; [ -f $O/prof/run_kernel_trace.csv ] && gzip -f $O/prof/run_kernel_trace.csv ;;
     pmc) bash tools/gpu_pmc.sh $TAG > $O/pmc.txt 2>&1; rc=$?; tail -40 $O/pmc.txt ;;
     ab:*) IFS=: read -r _ nr arms <<< "$step"; IFS='|' read -ra A <<< "$arms"
