@@ -4,6 +4,7 @@ Public modules:
   model_fibinet  -- build_model / MM_FiBiNET (drop-in for src/model_fibinet.py)
   trainer        -- FiBiNETTrainer: fused native train step (clip + Adam + OneCycleLR on device,
                     row-sharded multi-GPU)
+  metrics        -- DeviceMetrics: exact validation AUC + log-loss counted on the device
   utils          -- set_seed / compute_auc / compute_logloss (src/utils.py)
   data           -- MicroLens-shaped synthetic batches
 The compute lives in libfibinet_hip.so (csrc/, C ABI in include/fibinet.h).

@@ -138,6 +138,9 @@ SIGNATURES = {
     "fbn_bilinear_bwd": (I, [P, I, I, P, P, P, P, P, I, I, P]),
     "fbn_collate": (I, [P, I, P, P, I, I, P, P, P, P, P, LL, P, P, I, P, P, P, P, P, P, P, P, P]),
     "fbn_collate_zero_if": (I, [P, LL, P, P]),
+    "fbn_eval_pack": (I, [P, P, LL, P, P, P]),
+    "fbn_eval_workspace_size": (SZ, [LL]),
+    "fbn_eval_reduce": (I, [P, LL, P, SZ, P, P, P]),
     "fbn_plan_create": (I, [P]),
     "fbn_plan_destroy": (I, [P]),
     "fbn_plan_size": (I, [P]),

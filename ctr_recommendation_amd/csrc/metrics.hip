@@ -1,0 +1,398 @@
+// Device evaluation metrics: exact ROC-AUC and log-loss of a validation split, without pulling the
+// probabilities to the host (replaces the per-batch .cpu() + the float64 host argsort of
+// src/train_fibinet.py:133-146 with src/utils.py:18-32; DESIGN.md "device metrics").
+//
+// Key.  A probability p is fp32 in [0, 1]: its bit pattern is monotone in its value and at most
+// 0x3F800000 (< 2^30).  One uint32 per sample, key = (bits(p) << 1) | y.  The AUC is a counting
+// problem over the keys alone -- no payload, no float arithmetic:
+//   U2 = sum over positives of (2 * #negatives with a smaller score + #negatives with an equal score)
+//   auc = U2 / (2 n_pos n_neg)        (finished on the host as an exact integer division)
+//
+// Counting (not a sort).  The 30 score bits split into an 18-bit high part (the bucket) and a
+// 12-bit low part:
+//   A  eval_hist_kernel     (neg, pos) counts per bucket, summed per workgroup in an LDS table first
+//                           (validation scores pile into a few hundred buckets: one atomic per bucket
+//                           and workgroup), and the log-loss partial of each workgroup from the same read
+//   S  eval_scan_*          exclusive scan of the counts: each bucket's segment start, the negatives
+//                           below it, the list of non-empty buckets; the output record's counts and
+//                           the log-loss sum (partials in index order, one thread)
+//   B  eval_scatter_kernel  unstable counting scatter of (low, y) into the bucket segments (equal keys
+//                           are interchangeable, so stability is not needed); positions per workgroup
+//                           from the same LDS table, one returning global atomic per bucket
+//   C  eval_count_kernel    one workgroup per non-empty bucket at a time: LDS histogram of the low
+//                           part (2 x 4096 u32: a bucket may hold all n samples, so 32-bit counters),
+//                           one sweep accumulating pos * (2 * (neg_below + neg_less) + neg_equal) in
+//                           u64, one u64 atomic per workgroup
+// Every total is an integer sum, so it is independent of execution order: reproducible by
+// construction.  The log-loss is float64 with compute_logloss's semantics (clip to [1e-15, 1 - 1e-15],
+// one log per sample), summed as a fixed-shape tree whose shape depends on n only -- no float atomics.
+//
+// Bad inputs never trap: they set bits of the evaluator's status word (EV_BAD_*), the host raises.
+#include "common.h"
+#include <algorithm>
+
+#define EV_LO_BITS 12
+#define EV_NLO (1 << EV_LO_BITS)                 // low-part values per bucket
+#define EV_NB (1 << 18)                          // buckets (0x3F800000 >> 12 = 0x3F800 < 2^18)
+#define EV_MAX_BITS 0x3F800000u                  // bits(1.0f)
+#define EV_SCAN_BLOCKS (EV_NB / 1024)            // scan: 1024 buckets per workgroup of 256
+#define EV_LL_MAX 1024                           // log-loss partials (workgroups of pass A) at most
+#define EV_ELEMS_PER_BLOCK 4096                  // pass A / B: keys per workgroup before grid-striding
+#define EV_TAB 1024                              // pass A / B: per-workgroup LDS table of bucket counts (direct-mapped)
+#define EV_EMPTY 0xFFFFFFFFu
+#define EV_COUNT_THREADS 512
+#define EV_COUNT_BLOCKS 1024
+
+#define EV_BAD_NAN 1u
+#define EV_BAD_RANGE 2u
+#define EV_BAD_LABEL 4u
+#define EV_BAD_KEY 8u
+
+struct EvalRecord {
+  unsigned long long U2, n_pos, n_neg;
+  double logloss_sum;
+};
+
+// workspace layout (bytes from ws; every section 256-B aligned)
+#define EV_OFF_HIST 0                                        // [EV_NB][2] u32 {neg, pos}; zeroed per reduce
+#define EV_OFF_CURSOR (EV_OFF_HIST + (size_t)EV_NB * 8)      // [EV_NB] u32 segment start -> end after pass B
+#define EV_OFF_NEGB (EV_OFF_CURSOR + (size_t)EV_NB * 4)      // [EV_NB] u32 negatives in lower buckets
+#define EV_OFF_LIST (EV_OFF_NEGB + (size_t)EV_NB * 4)        // [EV_NB] u32 non-empty buckets, ascending
+#define EV_OFF_BSUM (EV_OFF_LIST + (size_t)EV_NB * 4)        // [EV_SCAN_BLOCKS][4] u32 {total, neg, non-empty}
+#define EV_OFF_NLIST (EV_OFF_BSUM + (size_t)EV_SCAN_BLOCKS * 16)   // u32 number of non-empty buckets
+#define EV_OFF_LL (EV_OFF_NLIST + 256)                       // [EV_LL_MAX] f64 log-loss partials
+#define EV_OFF_SEG (EV_OFF_LL + (size_t)EV_LL_MAX * 8)       // [n] u16 (low << 1) | y, grouped by bucket
+
+static inline int ev_stream_blocks(long long n) {
+  return (int)std::min<long long>(EV_LL_MAX, std::max<long long>(1, (n + EV_ELEMS_PER_BLOCK - 1) / EV_ELEMS_PER_BLOCK));
+}
+
+// exclusive prefix sum of v over a workgroup of NW waves (sh: NW words); total = the workgroup's sum
+template <int NW>
+__device__ __forceinline__ uint32_t ev_block_excl_scan(uint32_t v, uint32_t* sh, uint32_t& total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  uint32_t incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t t = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += t;
+  }
+  __syncthreads();                               // sh may still be read from the previous scan
+  if (lane == 63) sh[w] = incl;
+  __syncthreads();
+  uint32_t base = 0, tot = 0;
+#pragma unroll
+  for (int k = 0; k < NW; ++k) {
+    const uint32_t s = sh[k];
+    if (k < w) base += s;
+    tot += s;
+  }
+  total = tot;
+  return base + incl - v;
+}
+
+// ---------------------------------------------------------------- pack
+__global__ void __launch_bounds__(256) eval_pack_kernel(const float* __restrict__ probs, const float* __restrict__ labels,
+                                                        long long n, uint32_t* __restrict__ keys, unsigned* status) {
+  unsigned bad = 0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    float p = probs[i];
+    const float y = labels[i];
+    if (p != p) { bad |= EV_BAD_NAN; p = 0.f; }
+    else if (p < 0.f || p > 1.f) { bad |= EV_BAD_RANGE; p = p < 0.f ? 0.f : 1.f; }
+    if (y != 0.f && y != 1.f) bad |= EV_BAD_LABEL;
+    const uint32_t bits = p == 0.f ? 0u : __float_as_uint(p);     // -0.0 compares equal to 0.0
+    keys[i] = (bits << 1) | (y == 1.f ? 1u : 0u);
+  }
+  if (bad) atomicOr(status, bad);
+}
+
+// ---------------------------------------------------------------- pass A: bucket counts + log-loss partials
+// Validation scores pile into a few hundred neighbouring buckets, whose counters share a handful of
+// cache lines: the counts of a workgroup's keys are summed in a direct-mapped LDS table first (slot =
+// bucket mod EV_TAB, claimed by the first bucket that reaches it; a bucket that finds its slot taken by
+// another goes to the global word directly) and flushed as one atomic per bucket and workgroup.
+__global__ void __launch_bounds__(256) eval_hist_kernel(const uint32_t* __restrict__ keys, uint32_t n, uint32_t* hist,
+                                                        double* __restrict__ llpart, unsigned* status) {
+  __shared__ double red[256];
+  __shared__ uint32_t tkey[EV_TAB], tneg[EV_TAB], tpos[EV_TAB];
+  const int tid = threadIdx.x;
+  const uint32_t stride = gridDim.x * 256u;
+  double acc = 0.0;
+  unsigned bad = 0;
+  for (int k = tid; k < EV_TAB; k += 256) { tkey[k] = EV_EMPTY; tneg[k] = 0u; tpos[k] = 0u; }
+  __syncthreads();
+  for (uint32_t i = blockIdx.x * 256u + tid; i < n; i += stride) {
+    const uint32_t key = keys[i];
+    uint32_t bits = key >> 1;
+    const uint32_t y = key & 1u;
+    if (bits > EV_MAX_BITS) { bits = EV_MAX_BITS; bad = EV_BAD_KEY; }   // a key fbn_eval_pack did not write
+    const uint32_t b = bits >> EV_LO_BITS;                               // < EV_NB
+    double p = (double)__uint_as_float(bits);
+    p = fmin(fmax(p, 1e-15), 1.0 - 1e-15);
+    acc += log(y ? p : 1.0 - p);
+    const uint32_t slot = b & (EV_TAB - 1);
+    const uint32_t prev = atomicCAS(&tkey[slot], EV_EMPTY, b);
+    if (prev == EV_EMPTY || prev == b) atomicAdd(y ? &tpos[slot] : &tneg[slot], 1u);
+    else atomicAdd(&hist[2 * b + y], 1u);
+  }
+  __syncthreads();
+  for (int k = tid; k < EV_TAB; k += 256) {
+    const uint32_t b = tkey[k];
+    if (b != EV_EMPTY) {
+      if (tneg[k]) atomicAdd(&hist[2 * b], tneg[k]);
+      if (tpos[k]) atomicAdd(&hist[2 * b + 1], tpos[k]);
+    }
+  }
+  if (bad) atomicOr(status, bad);
+  red[tid] = acc;
+  __syncthreads();
+#pragma unroll
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) llpart[blockIdx.x] = red[0];
+}
+
+// ---------------------------------------------------------------- scan
+// thread t of workgroup g owns buckets g*1024 + 4t .. +3
+__device__ __forceinline__ void ev_load4(const uint32_t* hist, uint32_t b0, uint32_t* neg, uint32_t* pos) {
+  const uint4 lo = *reinterpret_cast<const uint4*>(hist + 2 * (size_t)b0);
+  const uint4 hi = *reinterpret_cast<const uint4*>(hist + 2 * (size_t)b0 + 4);
+  neg[0] = lo.x; pos[0] = lo.y; neg[1] = lo.z; pos[1] = lo.w;
+  neg[2] = hi.x; pos[2] = hi.y; neg[3] = hi.z; pos[3] = hi.w;
+}
+
+__global__ void __launch_bounds__(256) eval_scan_sums_kernel(const uint32_t* __restrict__ hist, uint32_t* __restrict__ bsum) {
+  __shared__ uint32_t sh[4];
+  uint32_t neg[4], pos[4];
+  ev_load4(hist, blockIdx.x * 1024u + threadIdx.x * 4u, neg, pos);
+  uint32_t tot = 0, ng = 0, ne = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { tot += neg[j] + pos[j]; ng += neg[j]; ne += (neg[j] + pos[j]) != 0; }
+  uint32_t t_tot, t_ng, t_ne;
+  ev_block_excl_scan<4>(tot, sh, t_tot);
+  ev_block_excl_scan<4>(ng, sh, t_ng);
+  ev_block_excl_scan<4>(ne, sh, t_ne);
+  if (threadIdx.x == 0) {
+    bsum[blockIdx.x * 4 + 0] = t_tot;
+    bsum[blockIdx.x * 4 + 1] = t_ng;
+    bsum[blockIdx.x * 4 + 2] = t_ne;
+  }
+}
+
+__global__ void __launch_bounds__(256) eval_scan_kernel(const uint32_t* __restrict__ hist, const uint32_t* __restrict__ bsum,
+                                                        uint32_t* __restrict__ cursor, uint32_t* __restrict__ negb,
+                                                        uint32_t* __restrict__ list, uint32_t* __restrict__ nlist,
+                                                        const double* __restrict__ llpart, int n_ll, EvalRecord* out) {
+  __shared__ uint32_t sh[4];
+  const int tid = threadIdx.x;
+  // the workgroups before this one (EV_SCAN_BLOCKS == 256 == the workgroup size)
+  const bool before = tid < (int)blockIdx.x;
+  uint32_t all_tot, all_ng, all_ne, b_tot, b_ng, b_ne, dummy;
+  const uint32_t s_tot = bsum[tid * 4 + 0], s_ng = bsum[tid * 4 + 1], s_ne = bsum[tid * 4 + 2];
+  ev_block_excl_scan<4>(s_tot, sh, all_tot);
+  ev_block_excl_scan<4>(s_ng, sh, all_ng);
+  ev_block_excl_scan<4>(s_ne, sh, all_ne);
+  ev_block_excl_scan<4>(before ? s_tot : 0u, sh, b_tot);
+  ev_block_excl_scan<4>(before ? s_ng : 0u, sh, b_ng);
+  ev_block_excl_scan<4>(before ? s_ne : 0u, sh, b_ne);
+  const uint32_t b0 = blockIdx.x * 1024u + tid * 4u;
+  uint32_t neg[4], pos[4];
+  ev_load4(hist, b0, neg, pos);
+  uint32_t tot = 0, ng = 0, ne = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { tot += neg[j] + pos[j]; ng += neg[j]; ne += (neg[j] + pos[j]) != 0; }
+  uint32_t r_tot = b_tot + ev_block_excl_scan<4>(tot, sh, dummy);
+  uint32_t r_ng = b_ng + ev_block_excl_scan<4>(ng, sh, dummy);
+  uint32_t r_ne = b_ne + ev_block_excl_scan<4>(ne, sh, dummy);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    cursor[b0 + j] = r_tot;
+    negb[b0 + j] = r_ng;
+    const uint32_t c = neg[j] + pos[j];
+    if (c) list[r_ne++] = b0 + j;                // r_ne < number of non-empty buckets <= EV_NB
+    r_tot += c;
+    r_ng += neg[j];
+  }
+  if (blockIdx.x == 0 && tid == 0) {
+    *nlist = all_ne;
+    out->U2 = 0ull;                              // pass C adds into it
+    out->n_pos = (unsigned long long)(all_tot - all_ng);
+    out->n_neg = (unsigned long long)all_ng;
+    double s = 0.0;                              // the partials in index order
+    for (int k = 0; k < n_ll; ++k) s += llpart[k];
+    out->logloss_sum = -s;
+  }
+}
+
+// ---------------------------------------------------------------- pass B: counting scatter
+// A workgroup takes EV_ELEMS_PER_BLOCK consecutive keys at a time: (1) counts them per bucket in the LDS
+// table (as pass A), (2) takes each bucket's base from its global cursor with one returning atomic,
+// (3) reads the keys again and hands out the positions from LDS.  A key whose slot another bucket holds
+// takes its position from the global cursor directly.
+__global__ void __launch_bounds__(256) eval_scatter_kernel(const uint32_t* __restrict__ keys, uint32_t n, uint32_t* cursor,
+                                                           uint16_t* __restrict__ seg) {
+  __shared__ uint32_t tkey[EV_TAB], tcnt[EV_TAB], tbase[EV_TAB];
+  const int tid = threadIdx.x;
+  for (int k = tid; k < EV_TAB; k += 256) { tkey[k] = EV_EMPTY; tcnt[k] = 0u; }
+  __syncthreads();
+  const uint32_t chunks = (n + EV_ELEMS_PER_BLOCK - 1) / EV_ELEMS_PER_BLOCK;
+  for (uint32_t c = blockIdx.x; c < chunks; c += gridDim.x) {            // workgroup-uniform
+    const uint32_t lo = c * (uint32_t)EV_ELEMS_PER_BLOCK;
+    const uint32_t hi = n - lo < (uint32_t)EV_ELEMS_PER_BLOCK ? n : lo + EV_ELEMS_PER_BLOCK;
+    for (uint32_t i = lo + tid; i < hi; i += 256) {
+      uint32_t bits = keys[i] >> 1;
+      if (bits > EV_MAX_BITS) bits = EV_MAX_BITS;                        // as pass A counted it
+      const uint32_t b = bits >> EV_LO_BITS, slot = b & (EV_TAB - 1);
+      const uint32_t prev = atomicCAS(&tkey[slot], EV_EMPTY, b);
+      if (prev == EV_EMPTY || prev == b) atomicAdd(&tcnt[slot], 1u);
+    }
+    __syncthreads();
+    for (int k = tid; k < EV_TAB; k += 256) {
+      const uint32_t cnt = tcnt[k];
+      if (cnt) { tbase[k] = atomicAdd(&cursor[tkey[k]], cnt); tcnt[k] = 0u; }
+    }
+    __syncthreads();
+    for (uint32_t i = lo + tid; i < hi; i += 256) {
+      const uint32_t key = keys[i];
+      uint32_t bits = key >> 1;
+      if (bits > EV_MAX_BITS) bits = EV_MAX_BITS;
+      const uint32_t b = bits >> EV_LO_BITS, slot = b & (EV_TAB - 1);
+      const uint16_t v = (uint16_t)(((bits & (EV_NLO - 1)) << 1) | (key & 1u));
+      uint32_t dst;
+      if (tkey[slot] == b) dst = tbase[slot] + atomicAdd(&tcnt[slot], 1u);
+      else dst = atomicAdd(&cursor[b], 1u);
+      if (dst < n) seg[dst] = v;                 // always true: the cursors partition [0, n)
+    }
+    __syncthreads();
+    for (int k = tid; k < EV_TAB; k += 256) tcnt[k] = 0u;                // the slots stay claimed
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------- pass C: per-bucket counting
+__global__ void __launch_bounds__(EV_COUNT_THREADS) eval_count_kernel(
+    const uint32_t* __restrict__ hist, const uint32_t* __restrict__ cursor, const uint32_t* __restrict__ negb,
+    const uint32_t* __restrict__ list, const uint32_t* __restrict__ nlist, const uint16_t* __restrict__ seg, uint32_t n,
+    EvalRecord* out) {
+  constexpr int NW = EV_COUNT_THREADS / 64, PER = EV_NLO / EV_COUNT_THREADS;
+  __shared__ uint32_t hneg[EV_NLO], hpos[EV_NLO];
+  __shared__ uint32_t sh[NW];
+  __shared__ unsigned long long red[NW];
+  const int tid = threadIdx.x, lane = tid & 63;
+  unsigned long long acc = 0ull;
+  const uint32_t nl = *nlist;
+  for (uint32_t li = blockIdx.x; li < nl; li += gridDim.x) {           // every branch below is workgroup-uniform
+    const uint32_t b = list[li];
+    const uint32_t cn = hist[2 * b], cp = hist[2 * b + 1];
+    const unsigned long long below = negb[b];
+    if (cp == 0) continue;                                             // negatives only: nothing to add
+    if (cn == 0) {                                                     // positives only: every lower negative counts twice
+      if (tid == 0) acc += (unsigned long long)cp * (2ull * below);
+      continue;
+    }
+    const uint32_t cnt = cn + cp, start = cursor[b] - cnt;             // pass B left each cursor at its segment's end
+    for (int k = tid; k < EV_NLO; k += EV_COUNT_THREADS) { hneg[k] = 0u; hpos[k] = 0u; }
+    __syncthreads();
+    for (uint32_t j0 = 0; j0 < cnt; j0 += EV_COUNT_THREADS) {
+      const uint32_t j = j0 + tid;
+      const bool valid = j < cnt && start + j < n;
+      const uint32_t v = valid ? (seg[start + j] & (2u * EV_NLO - 1u)) : 0u;   // (low << 1) | y: in range whatever seg holds
+      // a wave whose 64 values are equal (heavy ties) adds once
+      const uint32_t v0 = __shfl(v, 0, 64);
+      const bool same = __ballot(valid && v == v0) == ~0ull;
+      if (same) {
+        if (lane == 0) atomicAdd((v0 & 1u) ? &hpos[v0 >> 1] : &hneg[v0 >> 1], 64u);
+      } else if (valid) {
+        atomicAdd((v & 1u) ? &hpos[v >> 1] : &hneg[v >> 1], 1u);
+      }
+    }
+    __syncthreads();
+    uint32_t ng[PER], ps[PER], s = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) { ng[k] = hneg[tid * PER + k]; ps[k] = hpos[tid * PER + k]; s += ng[k]; }
+    uint32_t dummy;
+    unsigned long long less = below + ev_block_excl_scan<NW>(s, sh, dummy);
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      acc += (unsigned long long)ps[k] * (2ull * less + ng[k]);
+      less += ng[k];
+    }
+    __syncthreads();                                                   // the histograms are zeroed again next
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if (lane == 0) red[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long t = 0ull;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) t += red[k];
+    if (t) atomicAdd(&out->U2, t);
+  }
+}
+
+__global__ void eval_empty_kernel(EvalRecord* out) {
+  out->U2 = 0ull; out->n_pos = 0ull; out->n_neg = 0ull; out->logloss_sum = 0.0;
+}
+
+// ---------------------------------------------------------------- entry points
+extern "C" int fbn_eval_pack(const float* probs, const float* labels, long long n, uint32_t* keys_out, unsigned* status,
+                             void* stream) {
+  if (n <= 0) return FBN_OK;
+  if (!probs || !labels || !keys_out || !status) { fbn_set_error("fbn_eval_pack: null argument"); return FBN_ERR_ARG; }
+  if (n >= (1ll << 31)) { fbn_set_error("fbn_eval_pack: n must be below 2^31"); return FBN_ERR_ARG; }
+  const int blocks = (int)std::min<long long>(2048, (n + 255) / 256);
+  fbn_launch(eval_pack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, probs, labels, n, keys_out, status);
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}
+
+extern "C" size_t fbn_eval_workspace_size(long long n) {
+  if (n < 0) n = 0;
+  return EV_OFF_SEG + (((size_t)n * 2 + 255) & ~(size_t)255);
+}
+
+extern "C" int fbn_eval_reduce(const uint32_t* keys, long long n, void* ws, size_t ws_bytes, void* out, unsigned* status,
+                               void* stream) {
+  static_assert(EV_SCAN_BLOCKS == 256, "eval_scan_kernel reads one block sum per thread");
+  static_assert(sizeof(EvalRecord) == 32, "record layout");
+  hipStream_t st = (hipStream_t)stream;
+  if (!out || ((uintptr_t)out & 7)) { fbn_set_error("fbn_eval_reduce: out must be an 8-B aligned device record"); return FBN_ERR_ARG; }
+  if (n < 0 || n >= (1ll << 31)) { fbn_set_error("fbn_eval_reduce: need 0 <= n < 2^31"); return FBN_ERR_ARG; }
+  EvalRecord* rec = (EvalRecord*)out;
+  if (n == 0) {
+    fbn_launch(eval_empty_kernel, dim3(1), dim3(1), 0, st, rec);
+    FBN_CHECK_LAUNCH();
+    return FBN_OK;
+  }
+  if (!keys || !ws || !status || ((uintptr_t)ws & 15)) {
+    fbn_set_error("fbn_eval_reduce: keys, status and a 16-B aligned ws are required");
+    return FBN_ERR_ARG;
+  }
+  if (ws_bytes < fbn_eval_workspace_size(n)) { fbn_set_error("fbn_eval_reduce: ws smaller than fbn_eval_workspace_size(n)"); return FBN_ERR_ARG; }
+  char* w = (char*)ws;
+  uint32_t* hist = (uint32_t*)(w + EV_OFF_HIST);
+  uint32_t* cursor = (uint32_t*)(w + EV_OFF_CURSOR);
+  uint32_t* negb = (uint32_t*)(w + EV_OFF_NEGB);
+  uint32_t* list = (uint32_t*)(w + EV_OFF_LIST);
+  uint32_t* bsum = (uint32_t*)(w + EV_OFF_BSUM);
+  uint32_t* nlist = (uint32_t*)(w + EV_OFF_NLIST);
+  double* llpart = (double*)(w + EV_OFF_LL);
+  uint16_t* seg = (uint16_t*)(w + EV_OFF_SEG);
+  const uint32_t un = (uint32_t)n;
+  const int sb = ev_stream_blocks(n);            // depends on n only: the log-loss tree's shape
+  if (hipMemsetAsync(hist, 0, (size_t)EV_NB * 8, st) != hipSuccess) { fbn_set_error("fbn_eval_reduce: memset failed"); return FBN_ERR_LAUNCH; }
+  fbn_launch(eval_hist_kernel, dim3(sb), dim3(256), 0, st, keys, un, hist, llpart, status);
+  fbn_launch(eval_scan_sums_kernel, dim3(EV_SCAN_BLOCKS), dim3(256), 0, st, (const uint32_t*)hist, bsum);
+  fbn_launch(eval_scan_kernel, dim3(EV_SCAN_BLOCKS), dim3(256), 0, st, (const uint32_t*)hist, (const uint32_t*)bsum, cursor,
+             negb, list, nlist, (const double*)llpart, sb, rec);
+  fbn_launch(eval_scatter_kernel, dim3(sb), dim3(256), 0, st, keys, un, cursor, seg);
+  fbn_launch(eval_count_kernel, dim3(EV_COUNT_BLOCKS), dim3(EV_COUNT_THREADS), 0, st, (const uint32_t*)hist,
+             (const uint32_t*)cursor, (const uint32_t*)negb, (const uint32_t*)list, (const uint32_t*)nlist,
+             (const uint16_t*)seg, un, rec);
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}

@@ -17,8 +17,9 @@ Same surface and loop as the reference script:
   epochs x steps_per_epoch, pct_start 0.3, div 25, final_div 1000) (:74-92, :113-123) -- all inside
   FiBiNETTrainer's device step;
 * the epoch loop (:103-152): loss printed every 200 steps with the current lr, the epoch's mean
-  train loss, valid AUC (utils.compute_auc, :133-146), and the best-AUC checkpoint
-  (App. B keys, no ``module.`` prefix: :148-152).
+  train loss, valid AUC and log-loss (:133-146; counted on the device by metrics.DeviceMetrics, the
+  AUC equal to utils.compute_auc's double), and the best-AUC checkpoint (App. B keys, no
+  ``module.`` prefix: :148-152).
 
 What differs is underneath: batches come from the HBM-resident loader (loader.py: one collate
 launch per batch, no worker processes, no pageable copies); the loss is accumulated on the device
@@ -60,24 +61,15 @@ def set_seed(seed: int) -> None:
     torch.manual_seed(seed)
 
 
-def _gather_host(x: np.ndarray, world: int) -> np.ndarray:
-    if world == 1:
-        return x
-    import torch.distributed as dist
-    parts = [None] * world
-    dist.all_gather_object(parts, x)
-    return np.concatenate(parts)
-
-
 def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoint: Optional[str] = None,
         log=print, overrides: Optional[Dict] = None) -> Dict:
-    """Train as src/train_fibinet.py does; returns {"best_auc", "history": [(epoch, loss, auc)]}."""
+    """Train as src/train_fibinet.py does; returns {"best_auc", "history": [(epoch, loss, auc)],
+    "valid_logloss": [per epoch], "trainer"}."""
     import torch.distributed as dist
 
     from .loader import make_loaders
     from .model_fibinet import build_model
     from .trainer import FiBiNETTrainer
-    from .utils import compute_auc
 
     cfg, dataset_cfg, model_cfg = load_config(config)
     model_cfg = dict(model_cfg, **(overrides or {}))
@@ -104,7 +96,7 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
                              batch_size=train_loader.batch_size // world, device=device, rank=rank, world=world,
                              init_state=init, seed=seed, table_adam=str(model_cfg.get("table_adam", "lazy")))
     del init
-    best_auc, history = 0.0, []
+    best_auc, history, valid_logloss = 0.0, [], []
     ckpt = checkpoint or os.path.join("..", "checkpoints", "FiBiNET_best.pth")
     for epoch in range(n_epochs):
         t0 = time.perf_counter()
@@ -130,20 +122,18 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
         train_loader.check(world=world)
         avg_loss = float(total.item()) / steps if steps else 0.0
         dt = time.perf_counter() - t0
-        # validation (:133-146): eval-mode probabilities of the whole split, AUC on the host
-        ys, ps = [], []
-        for batch, labels in valid_loader:
-            ps.append(trainer.predict(batch).cpu().numpy())
-            ys.append(labels.cpu().numpy())
+        # validation (:133-146): eval-mode probabilities of the whole split, packed and counted on the
+        # device (metrics.DeviceMetrics: the exact AUC, the double utils.compute_auc returns on them)
+        ev = trainer.evaluate(valid_loader)
         valid_loader.check(world=world)
-        auc = None
-        if ys:
-            y = _gather_host(np.concatenate(ys), world)
-            p = _gather_host(np.concatenate(ps), world)
-            auc = float(compute_auc(y, p))
+        auc = logloss = None
+        if len(valid_loader):
+            auc, logloss = float(ev["auc"]), float(ev["logloss"])
         history.append((epoch + 1, avg_loss, auc))
+        valid_logloss.append(logloss)
         log0(f"Epoch {epoch + 1} | Train Loss: {avg_loss:.4f} | Valid AUC: {auc if auc is None else round(auc, 4)} | "
-             f"{steps * train_loader.batch_size / dt:.0f} samples/s")
+             f"{steps * train_loader.batch_size / dt:.0f} samples/s | "
+             f"Valid LogLoss: {logloss if logloss is None else round(logloss, 4)}")
         if auc is not None and auc > best_auc:
             best_auc = auc
             sd = trainer.state_dict()                     # collective at N > 1 (table on rank 0 only)
@@ -152,7 +142,7 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
                 torch.save(sd, ckpt)
                 log0(f"New best FiBiNET AUC; saved to {ckpt}")
     log0(f"Done. Best AUC: {best_auc:.4f}")
-    return {"best_auc": best_auc, "history": history, "trainer": trainer}
+    return {"best_auc": best_auc, "history": history, "valid_logloss": valid_logloss, "trainer": trainer}
 
 
 def main(argv=None):

@@ -425,6 +425,7 @@ class FiBiNETTrainer:
         self.xchg = RowExchange(rank, world, self.V, d, self.B, max_len, dev, group, stage_on_cpu=stage_on_cpu,
                                 rows_bf16=self.fcfg.bf16, side=self.side, comm=self.native_comm) if sharded else None
         self.stage_on_cpu = stage_on_cpu
+        self._eval_metrics = None          # evaluate()'s DeviceMetrics, kept between calls
         self.early_grad_xchg = _EARLY_GRAD_XCHG == "1"
         # item-table Adam: "lazy" (default) replays the zero-gradient steps of a row when the row
         # is next claimed or its rolling window comes round (bit-identical to eager; see
@@ -1275,6 +1276,38 @@ class FiBiNETTrainer:
             return torch.empty(0, dtype=torch.float32, device=self.device)
         a = ops.forward(self.p, batch, cfg, None, table_rows=rows, pos=pos, err=self.err)
         return (a["logits"] if logits else a["probs"]).clone()
+
+    @torch.no_grad()
+    def evaluate(self, loader_or_batches, metrics=None) -> Dict:
+        """Validation metrics of (batch, labels) pairs without a per-batch host transfer: predict()'s
+        eval-mode forward per batch, its probabilities packed straight into a metrics.DeviceMetrics
+        (one launch per batch), then one exact device reduce and one 40-byte read.  Returns
+        {"auc", "logloss", "n", "n_pos"}; the AUC is the double utils.compute_auc gives on the
+        concatenated predict() outputs (src/train_fibinet.py:133-146).  N > 1: collective exactly as
+        predict() is (a rank with an empty slice still joins) plus the key all-gather -- every rank
+        returns the global numbers.  metrics: a DeviceMetrics to fill (reset first; its capacity must
+        hold this rank's samples); default: one sized for the input, kept for the next call."""
+        from .metrics import DeviceMetrics
+        if metrics is None:
+            ds = getattr(loader_or_batches, "ds", None)
+            if ds is not None:                                # DeviceLoader: this rank's share of every batch
+                need = -(-len(ds) // self.world) + len(loader_or_batches)
+            else:
+                loader_or_batches = list(loader_or_batches)
+                need = sum(int(y.numel()) for _, y in loader_or_batches)
+            metrics = self._eval_metrics
+            if metrics is None or metrics.capacity < need:
+                self._eval_metrics = None
+                metrics = self._eval_metrics = DeviceMetrics(need, self.device)
+        metrics.reset()
+        for batch, labels in loader_or_batches:
+            probs = self.predict(batch)
+            if probs.numel():
+                metrics.update(probs, labels)
+        if self.world > 1:
+            group = self.group if self.group is not None else dist.group.WORLD
+            return metrics.compute(group=group, stage_on_cpu=self.stage_on_cpu)
+        return metrics.compute()
 
     def check_ids(self) -> None:
         """Raise what the reference would have raised since the last check (one 4-byte read):

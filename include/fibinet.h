@@ -624,6 +624,28 @@ int fbn_collate(const int64_t* perm, int B, const int64_t* item, const int64_t* 
  * (src/Prediction.py:39-42) on the batch's own missing flag, with no host round trip. */
 int fbn_collate_zero_if(float* x, long long n, const int* flag, void* stream);
 
+/* ---------------------------------------------------------------- device metrics (exact AUC + log-loss)
+ * Replaces the validation metric of src/train_fibinet.py:133-146 (every batch's probabilities copied
+ * to the host, then roc_auc_score / log_loss of src/utils.py:18-32) by integer counting on the device.
+ * One uint32 key per sample: key = (bits(p) << 1) | y for an fp32 probability p in [0, 1] (its bit
+ * pattern is monotone in its value, at most 0x3F800000) and a label y in {0, 1}.
+ * fbn_eval_pack: n keys at keys_out (the caller passes keys + count); no host sync.  A NaN p (bit 0),
+ * a p outside [0, 1] (bit 1) or a label that is neither 0.0 nor 1.0 (bit 2) sets that bit of *status
+ * (the evaluator's own word, not the trainer's err) and packs a clamped key -- nothing traps.
+ * fbn_eval_reduce: out = device record {uint64 U2; uint64 n_pos; uint64 n_neg; double logloss_sum}
+ * (32 B, 8-B aligned) over keys[0 .. n), 0 <= n < 2^31:
+ *   U2 = sum over positives of (2 * #negatives with a smaller score + #negatives with an equal score),
+ * exact and independent of the keys' order, so auc = U2 / (2 n_pos n_neg) (0.5 when a class is empty);
+ *   logloss_sum = sum of -(y log p + (1 - y) log(1 - p)) in float64 with p clipped to [1e-15, 1 - 1e-15]
+ * (src/utils.py:29-32), a fixed-shape tree over the key sequence (bitwise reproducible, no float atomics).
+ * A key above (0x3F800000 << 1) | 1 is counted as 1.0 and sets bit 3 of *status.  ws: >=
+ * fbn_eval_workspace_size(n) bytes (host-only query), 16-B aligned; the call zeroes what it needs. */
+int fbn_eval_pack(const float* probs, const float* labels, long long n, uint32_t* keys_out, unsigned* status,
+                  void* stream);
+size_t fbn_eval_workspace_size(long long n);
+int fbn_eval_reduce(const uint32_t* keys, long long n, void* ws, size_t ws_bytes, void* out, unsigned* status,
+                    void* stream);
+
 /* ---------------------------------------------------------------- step programs (native step driver)
  * Replaces the Python loop body that issues one training step (src/train_fibinet.py:113-123): the
  * host records a step's calls of this library -- entry point, arguments, and the cross-stream
