@@ -58,9 +58,12 @@ def build(verbose: bool = True) -> str:
     return LIB
 
 
-# A/B builds of the library (never the product): name -> preprocessor defines.  Built into
-# tools/variants/libfibinet_hip_<name>.so and selected with FBN_LIB_PATH (_lib.py).
+# A/B and tuning builds of the library (never the product): name -> preprocessor defines.  Built
+# into tools/variants/libfibinet_hip_<name>.so and selected with FBN_LIB_PATH (_lib.py).
 VARIANTS = {
+    # the GEMM plan overrides FBN_GEMM_FORCE / FBN_GEMM_NO_DMA16 of tools/gemm_sweep.py and
+    # tools/gemm_one.py (how plan_dma16 was tuned); the product does not read them
+    "sweep": ("FBN_SWEEP",),
     # table and dense Adam with correctly rounded sqrt / division, unfused (parity bisection)
     "ieee": ("FBN_ADAM_IEEE",),
     # the replay engine's constants one step at a time (round 4's form; A/B of FBN_REPLAY_BLOCK4)

@@ -60,8 +60,6 @@ struct FieldArgs {
   const int* hot;           // optional hot-row list (fbn_hot_rows) staged in LDS: [H] row ids
   const int* hot_n;         // its length (entries past H ignored)
   int H;
-  int abl;                  // measurement only (FBN_FIELDS_ABL, tools/time_fields.py): 1 = no history
-                            // loads, 2 = no field stores, 4 = no item / cate / mm loads; 0 = the real kernel
 };
 
 // hot-row staging (fbn_fields_fwd_hot, an A/B variant of the gather): up to FBN_HOT_ROWS(D) rows
@@ -186,17 +184,16 @@ __global__ void __launch_bounds__(256) fields_fwd_kernel(FieldArgs p) {
     // history rows are issued in chunks of HCH slots (all loads of a chunk in flight before
     // any is consumed) and summed in slot order like the reference's sum over dim 1
     // independent loads first (they overlap the row gather below)
-    const bool ld3 = !(p.abl & 4);
-    const f32x4 c1 = ld3 ? *reinterpret_cast<const f32x4*>(p.cate + lk * D + 4 * q) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    const f32x4 c2 = ld3 ? *reinterpret_cast<const f32x4*>(p.cate + vw * D + 4 * q) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    const f32x4 h = ld3 ? *reinterpret_cast<const f32x4*>(p.hmm + (size_t)b * D + 4 * q) : (f32x4){1.f, 2.f, 3.f, 4.f};
+    const f32x4 c1 = *reinterpret_cast<const f32x4*>(p.cate + lk * D + 4 * q);
+    const f32x4 c2 = *reinterpret_cast<const f32x4*>(p.cate + vw * D + 4 * q);
+    const f32x4 h = *reinterpret_cast<const f32x4*>(p.hmm + (size_t)b * D + 4 * q);
     f32x4 rit = {0.f, 0.f, 0.f, 0.f};
     f32x4 hs = {0.f, 0.f, 0.f, 0.f};
     int nnz = 0;
     const int* pb = MODE >= 1 ? p.pos + (size_t)b * (L + 1) : nullptr;
     if (MODE == 0) {
       if (item < 0 || item >= p.V) { bad = true; item = -1; }
-      if (item >= 0 && ld3) rit = *reinterpret_cast<const f32x4*>(p.table + item * D + 4 * q);
+      if (item >= 0) rit = *reinterpret_cast<const f32x4*>(p.table + item * D + 4 * q);
     } else {
       const int pi = pb[0];
       if (pi >= 0) rit = load_row<D, MODE>(p, pi, q);
@@ -262,7 +259,7 @@ __global__ void __launch_bounds__(256) fields_fwd_kernel(FieldArgs p) {
       __builtin_amdgcn_wave_barrier();                 // the next sample's list overwrites this one
       __atomic_signal_fence(__ATOMIC_SEQ_CST);
     }
-    for (int t0 = 0; t0 < ((CMP || (p.abl & 1)) ? 0 : L); t0 += HCH) {
+    for (int t0 = 0; t0 < (CMP ? 0 : L); t0 += HCH) {
       // branch-free: every slot of the chunk issues its load (a padding or past-L slot reads row
       // 0, an L2-resident line, and contributes +0 by a select) -- a load under a branch makes
       // hipcc drain vmcnt(0) before the next, which serialised the chunk's round trips
@@ -324,15 +321,13 @@ __global__ void __launch_bounds__(256) fields_fwd_kernel(FieldArgs p) {
 
     // ---------------- stores
     float* Xb = p.X + (size_t)b * 2 * D + 4 * q;
-    if (!(p.abl & 2)) {
-      *reinterpret_cast<f32x4*>(Xb) = rit;
-      *reinterpret_cast<f32x4*>(Xb + D) = x5;
-    }
+    *reinterpret_cast<f32x4*>(Xb) = rit;
+    *reinterpret_cast<f32x4*>(Xb + D) = x5;
     float* Vb = p.Vc ? p.Vc + (size_t)b * 5 * D + 4 * q : nullptr;
     float* cb = (p.c && !p.c16) ? (float*)p.c + (size_t)b * p.ldc + 4 * q : nullptr;
     short* cb16 = (p.c && p.c16) ? (short*)p.c + (size_t)b * p.ldc + 4 * q : nullptr;
 #pragma unroll
-    for (int f = 0; f < 5 && !(p.abl & 2); ++f) {
+    for (int f = 0; f < 5; ++f) {
       const f32x4 v = xs[f] * a[f + 1];
       if (p.Vc) *reinterpret_cast<f32x4*>(Vb + f * D) = v;   // bf16 mode: only the bf16 copies
       const bf16x4 v16 = (bf16x4){f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
@@ -659,29 +654,7 @@ struct GradOuts {
   float* p[8];
   int off[9];
 };
-// One launch: 64 columns per 1024-thread block, the 16 waves stride over the partial rows, a
-// fixed-order fold across the waves (deterministic), then each column to its destination.
-__global__ void __launch_bounds__(1024) reduce_partials_one(const float* __restrict__ part, int nblk, int P, GradOuts o) {
-  __shared__ float red[16][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + lane;
-  float s = 0.f;
-  if (i < P)
-    for (int r = w; r < nblk; r += 16) s += part[(size_t)r * P + i];
-  red[w][lane] = s;
-  __syncthreads();
-  if (w == 0 && i < P) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) t += red[k][lane];
-    int seg = 0;
-#pragma unroll
-    for (int j = 1; j < 8; ++j) seg += (i >= o.off[j]) ? 1 : 0;
-    if (o.p[seg]) o.p[seg][i - o.off[seg]] = t;
-  }
-}
-
-// Same reduction on 16 columns per block (P / 16 workgroups): 64 partial-row streams per column,
+// One launch, 16 columns per block (P / 16 workgroups): 64 partial-row streams per column,
 // 16 lanes reading one 64-B segment, then a fixed-order fold over the 64 streams (deterministic).
 __global__ void __launch_bounds__(1024) reduce_partials_one16(const float* __restrict__ part, int nblk, int P, GradOuts o) {
   __shared__ float red[64][16];
@@ -737,8 +710,7 @@ static int launch_fields_fwd_h(const FieldArgs& a, int D, hipStream_t st) {
   if constexpr (MODE == 0) {
     if (a.hot) return launch_fields_fwd_hb<0, HCH, true, true>(a, D, st);
     // buffer-resource history loads while the table's byte extent fits the descriptor's 32 bits
-    static const bool nobuf = getenv("FBN_FIELDS_NOBUF") != nullptr;   // A/B knob
-    if (!nobuf && (unsigned long long)a.V * D * 4 < 0xFFFFFF00ull)
+    if ((unsigned long long)a.V * D * 4 < 0xFFFFFF00ull)
       return launch_fields_fwd_hb<0, HCH, true, false, CMP>(a, D, st);
   }
   return launch_fields_fwd_hb<MODE, HCH, false, false, CMP>(a, D, st);
@@ -850,8 +822,6 @@ static int fields_fwd_impl(const int64_t* item_id, const int64_t* item_seq, cons
   a.map = map; a.slot_row = slot_row;
   a.V = V; a.B = B; a.L = L; a.ldc = ldc; a.R = R; a.n_cate = n_cate; a.ln_eps = ln_eps; a.c16 = c_bf16;
   a.hot = hot; a.hot_n = hot_n; a.H = H;
-  const char* ae = getenv("FBN_FIELDS_ABL");   // measurement only (NOT a valid forward when set)
-  a.abl = ae ? atoi(ae) : 0;
   if (pos && rows_bf16) return launch_fields_fwd<2>(a, D, (hipStream_t)stream);
   if (pos) return launch_fields_fwd<1>(a, D, (hipStream_t)stream);
   return launch_fields_fwd<0>(a, D, (hipStream_t)stream);
@@ -954,12 +924,7 @@ static int fields_bwd_impl(const int64_t* item_id, const int64_t* item_seq, cons
     o.p[j] = param_grads[j];   // [7] (mm_proj bias) may be null: not written
     o.off[j + 1] = o.off[j] + sizes[j];
   }
-  static const bool narrow = getenv("FBN_PARTIALS64") != nullptr;   // A/B knob: 64 columns per workgroup
-  if (narrow)
-    fbn_launch(reduce_partials_one, dim3(fbn_cdiv(P, 64)), dim3(1024), 0, st, (const float*)partials, nblk, P, o);
-  else
-    fbn_launch(reduce_partials_one16, dim3(fbn_cdiv(P, 16)), dim3(1024), 0, st, (const float*)partials, nblk, P,
-                       o);
+  fbn_launch(reduce_partials_one16, dim3(fbn_cdiv(P, 16)), dim3(1024), 0, st, (const float*)partials, nblk, P, o);
   FBN_CHECK_LAUNCH();
   return FBN_OK;
 }

@@ -821,7 +821,6 @@ struct GemmGroup {
   GemmArgs g[FBN_GEMM_GROUP_MAX];
   int tiles_n[FBN_GEMM_GROUP_MAX], tiles[FBN_GEMM_GROUP_MAX], start[FBN_GEMM_GROUP_MAX + 1];
   int n;
-  int remap;   // XCD-aware block order (FBN_GROUP_XCD=0: dispatch order, A/B)
 };
 template <int BM, int BN, bool AKM, bool BKM, int S, int WGM, int WGN, bool S3 = false>
 __global__ void __launch_bounds__(64 * WGM * WGN) gemm_dma16_group_kernel(GemmGroup G) {
@@ -830,7 +829,7 @@ __global__ void __launch_bounds__(64 * WGM * WGN) gemm_dma16_group_kernel(GemmGr
   // tile), so workgroups that share an operand panel of one K-slab meet in one L2: the launch's L2
   // fills 251 -> 115 MB for ~77 MB of operands (profiles/r03x_pmc_traffic.json); the time is
   // unchanged (0.4285 vs 0.4289 ms/step) -- the re-reads were served by the MALL
-  const int b = G.remap ? xcd_tile(blockIdx.x, gridDim.x) : blockIdx.x;
+  const int b = xcd_tile(blockIdx.x, gridDim.x);
   int p = 0;
 #pragma unroll
   for (int q = 1; q < FBN_GEMM_GROUP_MAX; ++q)
@@ -978,18 +977,7 @@ static GemmPlan plan_gemm(int M, int N, int K, int bk) {
 static GemmPlan plan_dma16(int M, int N, int K) {
   const long long t64 = (long long)fbn_cdiv(M, 64) * fbn_cdiv(N, 64);
   if (t64 >= 512) {
-    if (const char* e = getenv("FBN_DMA_BIG_TILE")) {   // tuning knob: "bm,bn" for large outputs
-      int a = 64, b = 64;
-      if (sscanf(e, "%d,%d", &a, &b) == 2) return {a, b, 1};
-    }
     if (N >= 1024 && (long long)fbn_cdiv(M, 128) * fbn_cdiv(N, 128) >= 256) return {128, 128, 1, 8};
-    // tuning knob: "bm,bn,waves" for an output whose 64x128 tiles leave fewer than two workgroups
-    // per CU (C3: MLP layer 2, 8192 x 256)
-    const char* mt = getenv("FBN_DMA_MID_TILE");
-    if (mt && (long long)fbn_cdiv(M, 64) * fbn_cdiv(N, 128) < 512) {
-      int a = 64, b = 128, w = 8;
-      if (sscanf(mt, "%d,%d,%d", &a, &b, &w) == 3) return {a, b, 1, w};
-    }
     if (N >= 128) return {64, 128, 1, 8};
     return {64, 64, 1};
   }
@@ -997,9 +985,8 @@ static GemmPlan plan_dma16(int M, int N, int K) {
   const long long tiles = (long long)fbn_cdiv(M, p.bm) * fbn_cdiv(N, p.bn);
   const long long target = p.bm == 128 ? 512 : 256;
   // a tiny output (the d x d / d x 128 weight gradients: 4 tiles) is latency-bound, not feed-bound:
-  // split K down to 2 K-steps per workgroup and keep a 4-deep ring (FBN_GEMM_TINY=0: the old rule)
-  const char* te = getenv("FBN_GEMM_TINY");
-  const bool tiny = tiles <= 16 && !(te && atoi(te) == 0);
+  // split K down to 2 K-steps per workgroup and keep a 4-deep ring
+  const bool tiny = tiles <= 16;
   const int min_k = tiny ? 128 : 256;
   while (p.split < 64 && tiles * p.split * 2 <= target && K / (p.split * 2) >= min_k) p.split *= 2;
   if (tiny) p.stages = 4;
@@ -1028,8 +1015,7 @@ static void launch_dma16(const GemmArgs& g, const GemmPlan& p, hipStream_t st) {
   const int tn = fbn_cdiv(g.N, BN), tm = fbn_cdiv(g.M, BM);
   const int nb = tn * tm;
   const int rx = nb >= 8 ? 1 : 0;
-  const char* e = getenv("FBN_GEMM_STAGES");   // tuning knob
-  const int S = e ? atoi(e) : (p.stages ? p.stages : FBN_DMA_STAGES);
+  const int S = p.stages ? p.stages : FBN_DMA_STAGES;
   const dim3 grid(nb, 1, p.split), blk(64 * WGM * WGN);
   if (g.s3k0) {   // split-bf16 x3 over two images per operand (two-stage ring only)
     fbn_launch((gemm_dma16_kernel<BM, BN, AKM, BKM, 2, WGM, WGN, true>), grid, blk, 0, st, g, tn, rx);
@@ -1223,8 +1209,6 @@ extern "C" int fbn_gemm_slabs_group(const void* descs, int n, void* stream) {
   if (!d || n > FBN_GEMM_GROUP_MAX) { fbn_set_error("fbn_gemm_slabs_group: 1 <= n <= 6 descriptors"); return FBN_ERR_ARG; }
   GemmGroup G;
   G.n = n;
-  const char* xe = getenv("FBN_GROUP_XCD");
-  G.remap = !(xe && atoi(xe) == 0);
   int big = 0;
   double fl = -1.0;
   for (int i = 0; i < n; ++i) {
@@ -1275,7 +1259,6 @@ extern "C" int fbn_gemm_slabs_group(const void* descs, int n, void* stream) {
   }
   G.start[n] = (int)total;
   hipStream_t st = (hipStream_t)stream;
-  const char* se = getenv("FBN_GROUP_STAGES");   // A/B knob: LDS-DMA ring depth of the group (2 or 3)
   if (d[0].s3k0 && wide)
     fbn_launch((gemm_dma16_group_kernel<128, 128, true, true, 2, 2, 4, true>), dim3((unsigned)total), dim3(512), 0,
                        st, G);
@@ -1284,12 +1267,6 @@ extern "C" int fbn_gemm_slabs_group(const void* descs, int n, void* stream) {
                        st, G);
   else if (wide && group_w4())   // A/B knob: 4 waves of 64x64 (fewer LDS fragment reads per MFMA)
     fbn_launch((gemm_dma16_group_kernel<128, 128, true, true, 2, 2, 2>), dim3((unsigned)total), dim3(256), 0,
-                       st, G);
-  else if (wide && se && atoi(se) == 4)
-    fbn_launch((gemm_dma16_group_kernel<128, 128, true, true, 4, 2, 4>), dim3((unsigned)total), dim3(512), 0,
-                       st, G);
-  else if (wide && se && atoi(se) == 3)
-    fbn_launch((gemm_dma16_group_kernel<128, 128, true, true, 3, 2, 4>), dim3((unsigned)total), dim3(512), 0,
                        st, G);
   else if (wide)
     fbn_launch((gemm_dma16_group_kernel<128, 128, true, true, 2, 2, 4>), dim3((unsigned)total), dim3(512), 0,
@@ -1344,8 +1321,11 @@ static int gemm_impl(const void* A, const void* B, float* C, const float* bias, 
   const int bk = bf16 == 1 ? 64 : 32;     // fp32 and split-bf16 (bf16 = 2) tiles are 32 deep
   // LDS-DMA path: bf16 operands, K % 64 == 0, 16-B rows; k-major operands need their
   // M / N extent in whole 8-element chunks
-  const bool dma16 = bf16 && a16 && b16 && rB_seg == 0x7fffffff && K % 64 == 0 && !(lda & 7) && !(ldb & 7) &&
-                     (!transA ? true : !(M & 7)) && (transB ? true : !(N & 7)) && !getenv("FBN_GEMM_NO_DMA16");
+  bool dma16 = bf16 && a16 && b16 && rB_seg == 0x7fffffff && K % 64 == 0 && !(lda & 7) && !(ldb & 7) &&
+               (!transA ? true : !(M & 7)) && (transB ? true : !(N & 7));
+#ifdef FBN_SWEEP   // build.py's "sweep" variant (tools/gemm_sweep.py, tools/gemm_one.py), never the product
+  if (getenv("FBN_GEMM_NO_DMA16")) dma16 = false;
+#endif
   if ((A2 || B2) && !dma16) {
     fbn_set_error("fbn_gemm_split: split operands need the bf16 LDS-DMA path (K % 64 == 0, bf16 operands)");
     return FBN_ERR_ARG;
@@ -1366,10 +1346,13 @@ static int gemm_impl(const void* A, const void* B, float* C, const float* bias, 
       return FBN_ERR_ARG;
     }
     p.split = slab_split(M, N, K);
-  } else if (const char* f = getenv("FBN_GEMM_FORCE")) {   // tuning sweeps only: "bm,bn,split[,waves[,stages]]"
+  }
+#ifdef FBN_SWEEP   // the sweep variant only: "bm,bn,split[,waves[,stages]]"
+  else if (const char* f = getenv("FBN_GEMM_FORCE")) {
     int a = 0, b = 0, c = 0, w = 4, sg = 0;
     if (sscanf(f, "%d,%d,%d,%d,%d", &a, &b, &c, &w, &sg) >= 3) p = {a, b, c, w, sg};
   }
+#endif
   g.stats = stats;
   if (p.split > 1 && (c16 || !ws || ws_bytes < (size_t)p.split * M * N * sizeof(float))) p.split = 1;
   int per = fbn_cdiv(K, p.split);

@@ -316,13 +316,8 @@ __device__ __forceinline__ float head_row(float s, int row, int lane, const Head
 // HEAD (C == 256, one column block): each wave holds whole rows, so the head Linear(256,1) +
 // sigmoid + BCE of src/model_fibinet.py:134,136 runs on the activations still in registers
 // (the same lane partials and reduction as head_fwd_kernel: bit-identical, one launch fewer).
-// BWD (HEAD, 1024 threads, one row per wave): the BN2 backward's column partials of the rank-1
-// source (fbn_bn_bwd_fused's first pass, bn_bwd_partial4) from the row's dL/dlogit, activation
-// and input while they are in registers: bpart[chunk][3][C] = {sum dy, sum (x-mean) dy,
-// sum gout*h}, dy = gout*w*(h > 0)*bscale, the same float products and f64 sums; waves folded in
-// a fixed order (deterministic).
-template <bool HEAD, int NT = 256, bool BWD = false>
-__global__ void __launch_bounds__(NT) bn_act_fwd2_kernel(const float* __restrict__ X, float* __restrict__ Y, int B,
+template <bool HEAD>
+__global__ void __launch_bounds__(256) bn_act_fwd2_kernel(const float* __restrict__ X, float* __restrict__ Y, int B,
                                                          int C, int rows_per_chunk, const float* __restrict__ mean,
                                                          const float* __restrict__ invstd,
                                                          const float* __restrict__ g, const float* __restrict__ bta,
@@ -330,10 +325,9 @@ __global__ void __launch_bounds__(NT) bn_act_fwd2_kernel(const float* __restrict
                                                          unsigned stream_id, unsigned char* __restrict__ mask_out,
                                                          const unsigned char* __restrict__ mask_in,
                                                          short* __restrict__ Y16, HeadArgs head,
-                                                         double* __restrict__ bpart = nullptr, float bscale = 1.f,
                                                          long long y16_lo = 0) {
   FBN_MAIN_PRIO();
-  constexpr int NWV = NT / 64;
+  constexpr int NWV = 4;
   const int q = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const int c = blockIdx.x * 256 + q * 4;
   if (c >= C) return;
@@ -348,7 +342,6 @@ __global__ void __launch_bounds__(NT) bn_act_fwd2_kernel(const float* __restrict
     alpha[e] = invstd[c + e] * g[c + e];
     bp[e] = bta[c + e] - mean[c + e] * alpha[e];
   }
-  double s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
   for (int r = r0 + rl; r < r1; r += NWV) {
     const size_t i = (size_t)r * C + c, i4 = i >> 2;
     const f32x4 x = *reinterpret_cast<const f32x4*>(X + i);
@@ -377,37 +370,7 @@ __global__ void __launch_bounds__(NT) bn_act_fwd2_kernel(const float* __restrict
     }
     if (HEAD) {
       const f32x4 ww = *reinterpret_cast<const f32x4*>(head.w + c);
-      const float go = head_row(y[0] * ww[0] + y[1] * ww[1] + y[2] * ww[2] + y[3] * ww[3], r, q, head);
-      if (BWD) {
-        const float gv = __shfl(go, 0, 64);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float d = gv * ww[e];
-          const float dy = y[e] > 0.f ? d * bscale : 0.f;
-          s0[e] += dy;
-          s1[e] += (double)((x[e] - mean[c + e]) * dy);
-          s2[e] += (double)(gv * y[e]);
-        }
-      }
-    }
-  }
-  if (BWD) {
-    // C == 256: lane q holds columns 4q..4q+3; fold the NWV waves per quantity through LDS
-    __shared__ double red[NWV][256];
-    double* pp = bpart + (size_t)blockIdx.y * 3 * C;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const double* sk = k == 0 ? s0 : (k == 1 ? s1 : s2);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) red[rl][q * 4 + e] = sk[e];
-      __syncthreads();
-      if (threadIdx.x < 256) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < NWV; ++w) t += red[w][threadIdx.x];
-        pp[(size_t)k * C + threadIdx.x] = t;
-      }
-      __syncthreads();
+      head_row(y[0] * ww[0] + y[1] * ww[1] + y[2] * ww[2] + y[3] * ww[3], r, q, head);
     }
   }
 }
@@ -847,46 +810,7 @@ __global__ void bn_moments_finalize_kernel(const double* __restrict__ mom, doubl
 }
 
 // Backward: chunk reduce of the three partial sums + the finalize of bn_bwd_finalize_kernel,
-// one wave per column (chunk_reduce_kernel's order).
-// 64 columns per 1024-thread block: lanes run along the columns (coalesced rows of the partial
-// slab), the 16 waves stride over the chunks, then a fixed-order fold across the waves
-// (deterministic) and the finalize.
-__global__ void __launch_bounds__(1024) bn_bwd_reduce_finalize_kernel(const double* __restrict__ part, int nchunk,
-                                                                      int C, double ntot,
-                                                                      const float* __restrict__ invstd, float* coef,
-                                                                      float* dgamma, float* dbeta, float* dw) {
-  __shared__ double red[16][3][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + lane;
-  double r0 = 0.0, r1 = 0.0, r2 = 0.0;
-  if (c < C) {
-    for (int k = w; k < nchunk; k += 16) {
-      const double* pk = part + (size_t)k * 3 * C + c;
-      r0 += pk[0];
-      r1 += pk[C];
-      r2 += pk[2 * C];
-    }
-  }
-  red[w][0][lane] = r0;
-  red[w][1][lane] = r1;
-  red[w][2][lane] = r2;
-  __syncthreads();
-  if (w == 0 && c < C) {
-    double r[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-      for (int k = 0; k < 16; ++k) r[q] += red[k][q][lane];
-    const float is = invstd[c];
-    const float sdy = (float)r[0], dotp = (float)r[1];
-    coef[c] = sdy / (float)ntot;
-    coef[C + c] = dotp * is * is / (float)ntot;
-    if (dgamma) dgamma[c] = dotp * is;
-    if (dbeta) dbeta[c] = sdy;
-    if (dw) dw[c] = (float)r[2];
-  }
-}
-
-// Same reduction on NC columns per block (C / NC workgroups instead of C / 64): 64 chunk streams
+// on NC columns per block (C / NC workgroups): 64 chunk streams
 // per column, NC lanes reading one row segment of the slab; then 48 NC threads fold the 64
 // streams of one (quantity, column) in fixed order (deterministic) and NC finalize.  The fold's
 // order does not depend on NC, so every NC gives the same bits (NC = 16 by default; FBN_BN_REDUCE_NC
@@ -1026,7 +950,6 @@ struct SumJobs {
   SlabJob s[FBN_MAX_SLAB_JOBS];
   int blk0[FBN_MAX_SLAB_JOBS + 1];   // first block of each slab job (after the column blocks)
   int ns;
-  int direct;                        // slab jobs of <= FBN_SLAB_DIRECT slabs: slab_direct
 };
 // slab jobs of at most FBN_SLAB_DIRECT slabs: one output quad per thread, every slab's load in
 // flight at once, summed in slab order (no LDS fold; a quarter of the blocks)
@@ -1054,7 +977,7 @@ __device__ __forceinline__ void slab_block(const SumJobs& J, int gb) {
   int u = 0;
   while (u + 1 < J.ns && gb >= J.blk0[u + 1]) ++u;
   const SlabJob sj = J.s[u];
-  if (J.direct && sj.nsplit <= FBN_SLAB_DIRECT) {
+  if (sj.nsplit <= FBN_SLAB_DIRECT) {
     slab_direct(sj, gb - J.blk0[u]);
     return;
   }
@@ -1340,12 +1263,7 @@ static bool bn_act_rows4() {
   const char* e = getenv("FBN_BN_ACT_R4");   // read per call
   return e && atoi(e) != 0;
 }
-static int bn_act_rows_per_chunk() {
-  const char* e = getenv("FBN_BN_ACT_RPC");   // A/B knob, read per call
-  const int v = e ? atoi(e) : 4;
-  const int rpc = v >= 4 && v % 4 == 0 ? v : 4;
-  return rpc;
-}
+#define FBN_BN_ACT_ROWS 4
 
 // rng: device [seed, offset] (uint64 x2) or null; mask_out (optional, u8 [B][C]) receives the keep-mask;
 // mask_in (optional, u8 [B][C]) replaces the RNG (parity tests against injected masks)
@@ -1363,10 +1281,10 @@ extern "C" int fbn_bn_act_fwd(const float* X, float* Y, int B, int C, const floa
     FBN_CHECK_LAUNCH();
     return FBN_OK;
   }
-  const int rpc = bn_act_rows_per_chunk();
+  const int rpc = FBN_BN_ACT_ROWS;
   fbn_launch(bn_act_fwd2_kernel<false>, dim3(fbn_cdiv(C, 256), fbn_cdiv(B, rpc)), dim3(256), 0,
                      (hipStream_t)stream, X, Y, B, C, rpc, mean, invstd, g, b, p_drop, rng, stream_id, mask_out, mask_in,
-                     Y16, HeadArgs{}, nullptr, 1.f, 0LL);
+                     Y16, HeadArgs{}, 0LL);
   FBN_CHECK_LAUNCH();
   return FBN_OK;
 }
@@ -1387,10 +1305,10 @@ extern "C" int fbn_bn_act_fwd_img(const float* X, float* Y, int B, int C, const 
     FBN_CHECK_LAUNCH();
     return FBN_OK;
   }
-  const int rpc = bn_act_rows_per_chunk();
+  const int rpc = FBN_BN_ACT_ROWS;
   fbn_launch(bn_act_fwd2_kernel<false>, dim3(fbn_cdiv(C, 256), fbn_cdiv(B, rpc)), dim3(256), 0,
                      (hipStream_t)stream, X, Y, B, C, rpc, mean, invstd, g, b, p_drop, rng, stream_id, mask_out, mask_in,
-                     (short*)Y_img, HeadArgs{}, nullptr, 1.f, (long long)B * C);
+                     (short*)Y_img, HeadArgs{}, (long long)B * C);
   FBN_CHECK_LAUNCH();
   return FBN_OK;
 }
@@ -1409,25 +1327,16 @@ extern "C" int fbn_bn_act_head_fwd(const float* X, float* Y, int B, int C, const
   if (bwd_part) {
     // the row chunks of fbn_bn_bwd_fused, so its reduce reads these partials as its own
     const int nch = bn_bwd_chunks(B, C), rpc = (B + nch - 1) / nch;
-    static const bool one_row = getenv("FBN_HEAD_ONE_ROW") != nullptr;   // A/B knob: one row per wave
-    if (!one_row) {
-      fbn_launch(bn_act_head_bwd4_kernel, dim3(1, fbn_cdiv(B, rpc)), dim3(256), 0, (hipStream_t)stream, X, Y, B,
-                 C, rpc, mean, invstd, g, b, p_drop, rng, stream_id, mask_out, mask_in,
-                 HeadArgs{hw, hbias, logits, probs, labels, loss_terms, gout, denom}, bwd_part, bwd_scale);
-      FBN_CHECK_LAUNCH();
-      return FBN_OK;
-    }
-    fbn_launch((bn_act_fwd2_kernel<true, 1024, true>), dim3(1, fbn_cdiv(B, rpc)), dim3(1024), 0,
-                       (hipStream_t)stream, X, Y, B, C, rpc, mean, invstd, g, b, p_drop, rng, stream_id, mask_out,
-                       mask_in, nullptr, HeadArgs{hw, hbias, logits, probs, labels, loss_terms, gout, denom}, bwd_part,
-                       bwd_scale, 0LL);
+    fbn_launch(bn_act_head_bwd4_kernel, dim3(1, fbn_cdiv(B, rpc)), dim3(256), 0, (hipStream_t)stream, X, Y, B,
+               C, rpc, mean, invstd, g, b, p_drop, rng, stream_id, mask_out, mask_in,
+               HeadArgs{hw, hbias, logits, probs, labels, loss_terms, gout, denom}, bwd_part, bwd_scale);
     FBN_CHECK_LAUNCH();
     return FBN_OK;
   }
-  const int rpc = bn_act_rows_per_chunk();
+  const int rpc = FBN_BN_ACT_ROWS;
   fbn_launch(bn_act_fwd2_kernel<true>, dim3(1, fbn_cdiv(B, rpc)), dim3(256), 0, (hipStream_t)stream, X, Y, B,
                      C, rpc, mean, invstd, g, b, p_drop, rng, stream_id, mask_out, mask_in, (short*)nullptr,
-                     HeadArgs{hw, hbias, logits, probs, labels, loss_terms, gout, denom}, nullptr, 1.f, 0LL);
+                     HeadArgs{hw, hbias, logits, probs, labels, loss_terms, gout, denom}, 0LL);
   FBN_CHECK_LAUNCH();
   return FBN_OK;
 }
@@ -1636,20 +1545,16 @@ static int bn_bwd_fused_impl(const float* G, const float* gvec, const float* w, 
   else
     fbn_launch(bn_bwd_partial4_kernel, dim3(fbn_cdiv(C, 256), nch), dim3(256), 0, st, s, Xpre, mean, B, C, rpc,
                        part);
-  static const bool wide = !getenv("FBN_BN_REDUCE64");   // A/B knob: 64 columns per workgroup
   const char* nce = getenv("FBN_BN_REDUCE_NC");   // A/B knob, read per call: columns per workgroup
   const int nc = nce ? atoi(nce) : 16;
-  if (wide && nc == 4)
+  if (nc == 4)
     fbn_launch(bn_bwd_reduce_finalize16_kernel<4>, dim3(fbn_cdiv(C, 4)), dim3(256), 0, st, part, nch, C, ntot,
                invstd, coef, dgamma, dbeta, dw);
-  else if (wide && nc == 8)
+  else if (nc == 8)
     fbn_launch(bn_bwd_reduce_finalize16_kernel<8>, dim3(fbn_cdiv(C, 8)), dim3(512), 0, st, part, nch, C, ntot,
                invstd, coef, dgamma, dbeta, dw);
-  else if (wide)
-    fbn_launch(bn_bwd_reduce_finalize16_kernel<16>, dim3(fbn_cdiv(C, 16)), dim3(1024), 0, st, part, nch, C, ntot,
-                       invstd, coef, dgamma, dbeta, dw);
   else
-    fbn_launch(bn_bwd_reduce_finalize_kernel, dim3(fbn_cdiv(C, 64)), dim3(1024), 0, st, part, nch, C, ntot,
+    fbn_launch(bn_bwd_reduce_finalize16_kernel<16>, dim3(fbn_cdiv(C, 16)), dim3(1024), 0, st, part, nch, C, ntot,
                        invstd, coef, dgamma, dbeta, dw);
   fbn_launch(bn_bwd_apply4_kernel, dim3(fbn_cdiv(C, 256), nch), dim3(256), 0, st, s, Xpre, mean, invstd, gamma,
                      coef, dXpre, dXpre16, B, C, rpc, colpart);
@@ -1685,8 +1590,6 @@ extern "C" int fbn_sum_jobs2(const SumJob* jobs, int n, const SlabJob* slabs, in
     J.col0[i + 1] = J.col0[i] + (jobs[i].C >= FBN_SUM_WIDE ? fbn_cdiv(jobs[i].C, 16) : jobs[i].C);
   }
   J.ns = ns;
-  const char* de = getenv("FBN_SLAB_DIRECT");   // A/B knob (0: the 4-group LDS fold for every slab job)
-  J.direct = !(de && atoi(de) == 0);
   J.blk0[0] = 0;
   for (int i = 0; i < ns; ++i) {
     const SlabJob& sj = slabs[i];
@@ -1696,7 +1599,7 @@ extern "C" int fbn_sum_jobs2(const SumJob* jobs, int n, const SlabJob* slabs, in
       return FBN_ERR_ARG;
     }
     J.s[i] = sj;
-    const int qpb = (J.direct && sj.nsplit <= FBN_SLAB_DIRECT) ? 256 : 64;   // output quads per block
+    const int qpb = (sj.nsplit <= FBN_SLAB_DIRECT) ? 256 : 64;   // output quads per block
     J.blk0[i + 1] = J.blk0[i] + (int)fbn_cdiv((long long)sj.M * sj.N / 4, qpb);
   }
   const int blocks = J.col0[n] + J.blk0[ns];

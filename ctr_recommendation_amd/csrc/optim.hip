@@ -1036,11 +1036,10 @@ __device__ __forceinline__ void wide_rows(int r, int key, int pe, int cnt, int T
   }
 }
 
-// items [0, n_ent): claiming entries (slot_row != -1); items [n_ent, n_ent + chunk): rows of the
-// rolling window not claimed this step.  nrows_total / F / chunk describe the window.
-// In-kernel row claims (single GPU, fbn_adam_claim_catchup): item != null -> entry e = b*(L+1)+t
-// claims its row as claim_rows_kernel does (first CAS wins; map, slot_row, dup written), and a
-// winning entry's row joins the replay at once -- one launch instead of claim + catch-up.
+// The entries of a batch and where their row claims go (adam_claim2, the prefetch kernels): entry
+// e = b*(L+1)+t claims its row as claim_rows_kernel does (first CAS wins; map, slot_row, dup
+// written), and a winning entry's row joins the replay at once -- one launch instead of claim +
+// catch-up.
 struct ClaimSrc {
   const int64_t* item;
   const int64_t* seq;
@@ -1060,14 +1059,15 @@ struct ClaimSrc {
   int skip0;
 };
 
+// The claimed rows' catch-up (fbn_adam_catchup, parts = 1): entry i of [0, n_ent) with
+// slot_row[i] != -1 brings its row up to the step.
 template <int D, bool DW>
 __global__ void __launch_bounds__(256) adam_catchup_kernel(float* __restrict__ p, float* __restrict__ m,
                                                            float* __restrict__ v, const int* __restrict__ slot_row,
-                                                           int n_ent, const int* __restrict__ map, long long nrows,
-                                                           int F, long long chunk, int parts, int* __restrict__ last,
+                                                           int n_ent, int F, int* __restrict__ last,
                                                            const AdamConsts* __restrict__ table,
                                                            const int* __restrict__ step, float wd, float b2,
-                                                           float omb2, float eps, PendSrc ps, ClaimSrc cs) {
+                                                           float omb2, float eps, PendSrc ps) {
   constexpr int G = D / 4, RPW = 64 / G;
   __shared__ AdamConsts win[FBN_LAZY_MAX_LAG];
   const int t = *step;
@@ -1079,14 +1079,11 @@ __global__ void __launch_bounds__(256) adam_catchup_kernel(float* __restrict__ p
     }
     __syncthreads();
   }
-  const long long roll0 = (long long)(t % F) * chunk;
-  const long long nroll = (parts & 2) && roll0 < nrows ? min(chunk, nrows - roll0) : 0;
-  if (!(parts & 1)) n_ent = 0;
-  const long long n = n_ent + nroll;
-  // Each wave takes SCAN items, one per lane, sorts them by replay start (rows that need no replay
+  const long long n = n_ent;
+  // Each wave takes SCAN entries, one per lane, sorts them by replay start (rows that need no replay
   // last) with a bitonic network over lane shuffles, and its RPW lane groups replay the sorted rows
   // RPW at a time: the rows of a round have similar replay lengths (their group finishes together)
-  // and duplicate / padding entries, claimed window rows and up-to-date rows cost nothing.
+  // and duplicate / padding entries and up-to-date rows cost nothing.
   // SCAN = 16 at D >= 64 gives ~10 waves per SIMD at C3, enough to hide each round's row loads.
   constexpr int SCAN = D >= 64 ? 16 : 64;
   const int lane = threadIdx.x & 63, q = lane % G, grp = lane / G;
@@ -1096,42 +1093,8 @@ __global__ void __launch_bounds__(256) adam_catchup_kernel(float* __restrict__ p
     const long long i = i0 + lane;
     int r = -1, key = 0x7fffffff, pe = -1;
     if (lane < SCAN && i < n) {
-      if (i < n_ent && cs.item) {
-        const long long b = i / (cs.L + 1), tt = i - b * (cs.L + 1);
-        const long long id = tt == 0 ? cs.item[b] : cs.seq[b * cs.L + (tt - 1)];
-        int owner = -1;
-        const unsigned long long pv = (cs.pre && id > 0 && id < cs.V) ? cs.pre[(size_t)(id) * FBN_RS_Q] : 0ull;
-        if ((int)(pv >> 32) == t && t > 0) {   // pre-claimed: the smallest entry index claims
-          owner = (int)(0xFFFFFFFFu - (unsigned)pv);
-          if (owner == (int)i) {
-            cs.map[id] = (int)i;
-            cs.slot_row[i] = (int)id;
-            r = (int)id;
-            owner = -1;
-          }
-        } else if (id > 0 && id < cs.V) {
-          // a popular row's later entries see its claim by a plain load: no CAS storm on one word
-          owner = __hip_atomic_load(cs.map + id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (owner == -1) {
-            int expected = -1;
-            if (__hip_atomic_compare_exchange_strong(cs.map + id, &expected, (int)i, __ATOMIC_RELAXED,
-                                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-              cs.slot_row[i] = (int)id;
-              r = (int)id;
-            } else {
-              owner = expected;
-            }
-          }
-        }
-        if (cs.dup) cs.dup[i] = owner;
-        if (cs.hasdup && owner >= 0) cs.hasdup[owner] = 1;
-      } else if (i < n_ent) {
-        const int sr = slot_row[i];
-        if (sr != -1) r = sr & ~FBN_SLOT_FLAG;
-      } else {
-        const long long rr = roll0 + (i - n_ent);
-        if (!map || map[rr] == -1) r = (int)rr;   // claimed rows are replayed by their claiming entry
-      }
+      const int sr = slot_row[i];
+      if (sr != -1) r = sr & ~FBN_SLOT_FLAG;
       if (r >= 0) {
         const int k0 = last[(size_t)(r) * FBN_RS_I];
         if (k0 < t) {
@@ -1288,12 +1251,8 @@ __device__ __forceinline__ long long entry_row(const ClaimSrc& cs, long long i) 
 // posted value is the same maximum as per-entry posting: bit-identical pre-claims.
 #define FBN_PRETAG_BLOCK 1024
 #define FBN_PRETAG_SLOTS 2048   // open addressing, load factor <= 1/2
-static int pretag_flat() {
-  static const int f = getenv("FBN_PRETAG_FLAT") && atoi(getenv("FBN_PRETAG_FLAT")) == 1;
-  return f;
-}
 __global__ void __launch_bounds__(FBN_PRETAG_BLOCK) adam_pretag_kernel(ClaimSrc cs, int n,
-                                                                        const int* __restrict__ step, int flat) {
+                                                                        const int* __restrict__ step) {
   __shared__ int hkey[FBN_PRETAG_SLOTS];
   __shared__ int hval[FBN_PRETAG_SLOTS];
   for (int k = threadIdx.x; k < FBN_PRETAG_SLOTS; k += blockDim.x) {
@@ -1303,11 +1262,6 @@ __global__ void __launch_bounds__(FBN_PRETAG_BLOCK) adam_pretag_kernel(ClaimSrc 
   __syncthreads();
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long id = i < n ? entry_row(cs, i) : -1;
-  if (flat) {   // A/B (FBN_PRETAG_FLAT=1): round 4's one global atomic per entry
-    if (id >= 0)
-      atomicMax(cs.pre + (size_t)id * FBN_RS_Q, ((unsigned long long)(*step + 1) << 32) | (0xFFFFFFFFull - (unsigned long long)i));
-    return;
-  }
   if (id >= 0) {   // (local rows and entry indices fit 31 bits: V, n < 2^31)
     unsigned h = ((unsigned)id * 2654435761u) >> (32 - 11);
     for (;;) {
@@ -1373,20 +1327,14 @@ __device__ __forceinline__ f32x4 consts4(const AdamConsts& k) { return (f32x4){k
 #endif
 // One group of the replay engine: G wave-wide rows (cur, rows cr, replay starts ck, deferred
 // vectors cp; slots past cnt carry row 0 and no steps) brought to T, then stored.
-// ABL (measurement only, tools/pf_ablation.py): 1 = no arithmetic (rows loaded and stored as they
-// are), 2 = no row traffic (zero rows, stores behind a run-time false flag); 0 = the real replay
-template <int D, bool DW, int G, int ABL = 0>
-__device__ __forceinline__ void replay_group(WideRow<D> (&cur)[G], const int (&cr)[G], const int (&ck)[G],
-                                             const int (&cp)[G], int j0, int cnt, int T, float* __restrict__ p,
-                                             float* __restrict__ m, float* __restrict__ v,
-                                             const AdamConsts* __restrict__ table, float wd, float b2, float omb2,
-                                             float eps, int lane, bool sink = true) {
-  if constexpr (ABL == 1) {
-#pragma unroll
-    for (int x = 0; x < G; ++x)
-      if (j0 + x < cnt) wide_store<D>(cur[x], p, m, v, cr[x], lane);
-    return;
-  }
+#define FBN_REPLAY_G 4   // rows per group: eight independent update chains per lane at D = 128
+template <int D, bool DW>
+__device__ __forceinline__ void replay_group(WideRow<D> (&cur)[FBN_REPLAY_G], const int (&cr)[FBN_REPLAY_G],
+                                             const int (&ck)[FBN_REPLAY_G], const int (&cp)[FBN_REPLAY_G], int j0,
+                                             int cnt, int T, float* __restrict__ p, float* __restrict__ m,
+                                             float* __restrict__ v, const AdamConsts* __restrict__ table, float wd,
+                                             float b2, float omb2, float eps, int lane) {
+  constexpr int G = FBN_REPLAY_G;
   typedef typename WideRow<D>::V V;
   constexpr int N = WideRow<D>::N;
   const V zero = {};
@@ -1460,20 +1408,19 @@ __device__ __forceinline__ void replay_group(WideRow<D> (&cur)[G], const int (&c
 #endif
 #pragma unroll
   for (int x = 0; x < G; ++x)
-    if (j0 + x < cnt && (ABL != 2 || sink)) wide_store<D>(cur[x], p, m, v, cr[x], lane);
+    if (j0 + x < cnt) wide_store<D>(cur[x], p, m, v, cr[x], lane);
 }
 
 // The replay engine of the two-pass prefetch and the window pass: a wave's rows (one per lane:
 // row r, first zero-gradient step key -- INT_MAX = none --, deferred vector pe), sorted by key,
-// brought to T steps G at a time, the next group's loads in flight while one replays.
-// G = 4 by default; G = 2 holds half the rows' registers (a smaller footprint beside the main
-// stream's kernels, fewer independent update chains per lane).
-template <int D, bool DW, int G = 4, int ABL = 0>
+// brought to T steps FBN_REPLAY_G at a time, the next group's loads in flight while one replays.
+template <int D, bool DW>
 __device__ __forceinline__ void replay4_sorted(int r, int key, int pe, int cnt, int T, int w0,
                                                const f32x4* __restrict__ win, float* __restrict__ p,
                                                float* __restrict__ m, float* __restrict__ v,
                                                const AdamConsts* __restrict__ table, float wd, float b2,
                                                float omb2, float eps, const PendSrc& ps, int lane) {
+  constexpr int G = FBN_REPLAY_G;
   // ascending replay start (descending replay length); rows past cnt last
 #pragma unroll
   for (int kk = 2; kk <= 64; kk <<= 1)
@@ -1503,20 +1450,14 @@ __device__ __forceinline__ void replay4_sorted(int r, int key, int pe, int cnt, 
 #pragma unroll
     for (int x = 0; x < G; ++x) {
       get(j + x, g.r[x], g.k[x], g.p[x]);
-      if constexpr (ABL == 2) {
-        g.w[x].p = g.w[x].m = g.w[x].v = g.w[x].g = (typename WideRow<D>::V){};
-        g.w[x].c = 1.f;
-      } else {
-        wide_load<D>(g.w[x], p, m, v, g.r[x], g.p[x] >= 0 ? g.k[x] - 1 : g.k[x], g.p[x], ps, lane);
-      }
+      wide_load<D>(g.w[x], p, m, v, g.r[x], g.p[x] >= 0 ? g.k[x] - 1 : g.k[x], g.p[x], ps, lane);
     }
   };
   Grp a, b;
   fill(a, 0);
   for (int j0 = 0; j0 < cnt; j0 += G) {
     fill(b, j0 + G);
-    replay_group<D, DW, G, ABL>(a.w, a.r, a.k, a.p, j0, cnt, T, p, m, v, table, wd, b2, omb2, eps, lane,
-                                ABL != 2 || wd == 12345.f);
+    replay_group<D, DW>(a.w, a.r, a.k, a.p, j0, cnt, T, p, m, v, table, wd, b2, omb2, eps, lane);
     a = b;
   }
 }
@@ -1603,17 +1544,17 @@ __device__ __forceinline__ void replay_narrow_sorted(int r, int key, int pe, int
   }
 }
 
-template <int D, bool DW, int G = 4, int ABL = 0>
+template <int D, bool DW>
 __device__ __forceinline__ void replay_sorted(int r, int key, int pe, int cnt, int T, int w0,
                                               const f32x4* __restrict__ win, float* __restrict__ p,
                                               float* __restrict__ m, float* __restrict__ v,
                                               const AdamConsts* __restrict__ table, float wd, float b2, float omb2,
                                               float eps, const PendSrc& ps, int lane) {
-  if constexpr (D >= 128) replay4_sorted<D, DW, G, ABL>(r, key, pe, cnt, T, w0, win, p, m, v, table, wd, b2, omb2, eps, ps, lane);
+  if constexpr (D >= 128) replay4_sorted<D, DW>(r, key, pe, cnt, T, w0, win, p, m, v, table, wd, b2, omb2, eps, ps, lane);
   else replay_narrow_sorted<D, DW>(r, key, pe, cnt, T, w0, win, p, m, v, table, wd, b2, omb2, eps, ps, lane);
 }
 
-template <int D, bool DW, int G = 4, int ABL = 0>
+template <int D, bool DW>
 __device__ __forceinline__ void adam_prefetch2_body(float* __restrict__ p, float* __restrict__ m,
                                                     float* __restrict__ v, const ClaimSrc& cs, int n,
                                                     int* __restrict__ last, const AdamConsts* __restrict__ table,
@@ -1626,8 +1567,8 @@ __device__ __forceinline__ void adam_prefetch2_body(float* __restrict__ p, float
     for (int s = threadIdx.x; s <= T - w0; s += blockDim.x) win[s] = consts4(table[w0 + s]);
   const int lane = threadIdx.x & 63;
   if constexpr (D < 128) __syncthreads();   // the LDS window (no barrier after this point)
-  // epw entries per wave (lanes past epw hold none); a capped grid (FBN_PF_WAVES) walks the
-  // entry chunks wave-strided, so the side stream holds few wave slots per SIMD at a time
+  // epw entries per wave (lanes past epw hold none); a grid smaller than the entry chunks walks
+  // them wave-strided
   const long long nchunk = ((long long)n + epw - 1) / epw;
   const long long wstride = ((long long)nblk * blockDim.x) >> 6;
   for (long long ch = ((long long)blk * blockDim.x + threadIdx.x) >> 6; ch < nchunk; ch += wstride) {
@@ -1652,18 +1593,17 @@ __device__ __forceinline__ void adam_prefetch2_body(float* __restrict__ p, float
   }
   const int cnt = __popcll(__ballot(key != 0x7fffffff));
   if (cnt == 0) continue;
-  replay_sorted<D, DW, G, ABL>(r, key, pe, cnt, T, w0, win, p, m, v, table, wd, b2, omb2, eps, ps, lane);
+  replay_sorted<D, DW>(r, key, pe, cnt, T, w0, win, p, m, v, table, wd, b2, omb2, eps, ps, lane);
   }
 }
-template <int D, bool DW, int G = 4, int ABL = 0>
+template <int D, bool DW>
 __global__ void __launch_bounds__(256) adam_prefetch2_kernel(float* __restrict__ p, float* __restrict__ m,
                                                              float* __restrict__ v, ClaimSrc cs, int n,
                                                              int* __restrict__ last,
                                                              const AdamConsts* __restrict__ table,
                                                              const int* __restrict__ step, float wd, float b2,
                                                              float omb2, float eps, PendSrc ps, int epw) {
-  adam_prefetch2_body<D, DW, G, ABL>(p, m, v, cs, n, last, table, step, wd, b2, omb2, eps, ps, epw, blockIdx.x,
-                                     gridDim.x);
+  adam_prefetch2_body<D, DW>(p, m, v, cs, n, last, table, step, wd, b2, omb2, eps, ps, epw, blockIdx.x, gridDim.x);
 }
 
 // ---- The prefetch with its replay balanced longest-first (fbn_adam_prefetch_binned, D >= 128).
@@ -1739,7 +1679,7 @@ __global__ void __launch_bounds__(256) adam_pfbin_kernel(ClaimSrc cs, int n, int
 // copy c8 ascending); waves past the last chunk exit.  The counts are zeroed by the next call's
 // pfb_zero.  ch = 32 by default: about as many waves as adam_prefetch2's (64 entries -> ~31 rows
 // each); chunks of 64 halve the waves and measured 0.474 vs 0.431 ms/step (fewer chains in flight).
-template <int D, bool DW, int G = 4>
+template <int D, bool DW>
 __global__ void __launch_bounds__(256) adam_pfreplay_kernel(float* __restrict__ p, float* __restrict__ m,
                                                             float* __restrict__ v, const int* __restrict__ step,
                                                             float wd, float b2, float omb2, float eps,
@@ -1789,7 +1729,7 @@ __global__ void __launch_bounds__(256) adam_pfreplay_kernel(float* __restrict__ 
     key = rec.y;
     pe = rec.z;
   }
-  replay4_sorted<D, DW, G>(r, key, pe, cnt, T, 0, nullptr, p, m, v, table, wd, b2, omb2, eps, ps, lane);
+  replay4_sorted<D, DW>(r, key, pe, cnt, T, 0, nullptr, p, m, v, table, wd, b2, omb2, eps, ps, lane);
 }
 
 __global__ void pfb_zero_kernel(unsigned* __restrict__ counts) {
@@ -1802,7 +1742,7 @@ __global__ void pfb_zero_kernel(unsigned* __restrict__ counts) {
 // in ONE round trip right after the id (they depend on the id only; nothing else writes them while
 // this kernel runs: the previous step's side work was joined before its step tail, this step's starts
 // after the claims), instead of id -> tag -> claim -> last -> pend one after another; the rows that
-// are behind are replayed by the four-row engine.  Claims are those of adam_catchup_kernel (tagged
+// are behind are replayed by the four-row engine.  Claims are those of claim_rows_kernel (a tagged
 // pre-claim, else plain load + CAS; dup / hasdup written the same way).
 template <int D, bool DW>
 __device__ __forceinline__ void adam_claim2_body(float* __restrict__ p, float* __restrict__ m,
@@ -1909,9 +1849,9 @@ __global__ void __launch_bounds__(256) convert_bf16_kernel_o(ConvJobs jobs, int 
 // The rolling window (step mod F) with the replay engine: rpw rows per wave
 // (one per lane), so a window of ~1e5 rows (C5's 12.5 M-row shard: 97.7 K rows replaying up to F
 // steps each) spreads over thousands of waves instead of one wave per SIMD; claimed rows are left
-// to their claiming entry, as in adam_catchup_kernel.
+// to their claiming entry.
 #define FBN_WIN_ROWS 16
-template <int D, bool DW, int G = 4>
+template <int D, bool DW>
 __device__ __forceinline__ void adam_window2_body(float* __restrict__ p, float* __restrict__ m,
                                                   float* __restrict__ v, const int* __restrict__ map,
                                                   long long nrows, int F, long long chunk, int* __restrict__ last,
@@ -1927,7 +1867,7 @@ __device__ __forceinline__ void adam_window2_body(float* __restrict__ p, float* 
   const long long nroll = roll0 < nrows ? min(chunk, nrows - roll0) : 0;
   const int lane = threadIdx.x & 63;
   if constexpr (D < 128) __syncthreads();   // the LDS window (no barrier after this point)
-  // rpw rows per wave; a capped grid (FBN_WIN_WAVES) walks the row groups wave-strided
+  // rpw rows per wave; a grid smaller than the row groups walks them wave-strided
   const long long ngrp = (nroll + rpw - 1) / rpw;
   const long long wstride = ((long long)nblk * blockDim.x) >> 6;
   for (long long gq = ((long long)blk * blockDim.x + threadIdx.x) >> 6; gq < ngrp; gq += wstride) {
@@ -1949,18 +1889,18 @@ __device__ __forceinline__ void adam_window2_body(float* __restrict__ p, float* 
   }
   const int cnt = __popcll(__ballot(key != 0x7fffffff));
   if (cnt == 0) continue;
-  replay_sorted<D, DW, G>(r, key, pe, cnt, t, w0, win, p, m, v, table, wd, b2, omb2, eps, ps, lane);
+  replay_sorted<D, DW>(r, key, pe, cnt, t, w0, win, p, m, v, table, wd, b2, omb2, eps, ps, lane);
   }
 }
-template <int D, bool DW, int G = 4>
+template <int D, bool DW>
 __global__ void __launch_bounds__(256) adam_window2_kernel(float* __restrict__ p, float* __restrict__ m,
                                                            float* __restrict__ v, const int* __restrict__ map,
                                                            long long nrows, int F, long long chunk,
                                                            int* __restrict__ last, const AdamConsts* __restrict__ table,
                                                            const int* __restrict__ step, float wd, float b2,
                                                            float omb2, float eps, PendSrc ps, int rpw) {
-  adam_window2_body<D, DW, G>(p, m, v, map, nrows, F, chunk, last, table, step, wd, b2, omb2, eps, ps, rpw,
-                              blockIdx.x, gridDim.x);
+  adam_window2_body<D, DW>(p, m, v, map, nrows, F, chunk, last, table, step, wd, b2, omb2, eps, ps, rpw,
+                           blockIdx.x, gridDim.x);
 }
 
 // every row up to `step` (checkpoint / evaluation)
@@ -2642,8 +2582,7 @@ extern "C" int fbn_adam_table(float* p, float* m, float* v, long long nrows, int
   const float omb2 = (float)(1.0 - (double)beta2);
   const AdamConsts* t = (const AdamConsts*)consts_table;
   const GradSrc s = make_src(gvec, extra, slot_row, Lp1);
-  static const int throttle = getenv("FBN_ADAM_BLOCKS") ? atoi(getenv("FBN_ADAM_BLOCKS")) : 512;   // tuning knob
-  const dim3 grid = mode == 1 ? dim3(throttle) : group_grid(nrows, D, 16384);
+  const dim3 grid = mode == 1 ? dim3(512) : group_grid(nrows, D, 16384);
   if (mode == 1 || mode == 2) {
     FBN_DISPATCH_D(adam_table_untouched, D, grid, p, m, v, nrows, map, s, coef, t, step, wd, beta2, omb2, eps);
   } else {
@@ -2712,10 +2651,8 @@ extern "C" int fbn_adam_step_tail(float* dp, const float* dg, float* dm, float* 
   const StepEnd se{step, rng, (double*)sumsq, nbt0, nbt1, ticket, max_step, err};
   long long nd = (n_dense / 4 + 255) / 256;
   // block caps (every block draws the step-end ticket; two-level, so ~16x less contention than
-  // one word): FBN_TAIL_ND / FBN_TAIL_NC, A/B knobs read per call
-  const char* ndc = getenv("FBN_TAIL_ND");
-  const char* ncc = getenv("FBN_TAIL_NC");
-  const long long cap_d = ndc ? atoll(ndc) : 256, cap_c = ncc ? atoll(ncc) : 1024;   // A/B: nc 1024 -5 us
+  // one word)
+  const long long cap_d = 256, cap_c = 1024;   // A/B: nc 1024 -5 us
   if (nd > cap_d) nd = cap_d;
   if (nd < 1) nd = 1;
   long long nc = ((long long)(n > 0 ? n : 1) + 255) / 256;
@@ -2752,7 +2689,7 @@ extern "C" int fbn_step_end(int* step, unsigned long long* rng, double* sumsq, l
 // lazy table Adam: replay the zero-loss-gradient steps of the claimed rows and of rolling window
 // (step mod F) (chunk = ceil(nrows / F) rows) up to `step`; last: [nrows] steps applied per row
 // parts: 1 = the claimed rows (must precede the gather), 2 = the rolling window (unclaimed rows:
-// nothing else reads them this step -> may run on a side stream), 3 = both
+// nothing else reads them this step -> may run on a side stream); any other value is FBN_ERR_ARG
 extern "C" int fbn_adam_catchup(float* p, float* m, float* v, long long nrows, int D, const int* slot_row, int n_ent,
                                 const int* map, int F, int parts, int* last, const void* consts_table, const int* step,
                                 float wd, float beta2, float eps, int* pend, const float* ring,
@@ -2760,51 +2697,26 @@ extern "C" int fbn_adam_catchup(float* p, float* m, float* v, long long nrows, i
                                 void* stream) {
   if (nrows <= 0) return FBN_OK;
   if (F < 1 || F > FBN_LAZY_MAX_LAG) { fbn_set_error("fbn_adam_catchup: 1 <= F <= 512"); return FBN_ERR_ARG; }
+  if (parts != 1 && parts != 2) {   // before any device work
+    fbn_set_error("fbn_adam_catchup: parts is 1 (claimed rows) or 2 (rolling window), one launch each");
+    return FBN_ERR_ARG;
+  }
   hipStream_t st = (hipStream_t)stream;
   const float omb2 = (float)(1.0 - (double)beta2);
   const long long chunk = (nrows + F - 1) / F;
-  const long long items = ((parts & 1) ? n_ent : 0) + ((parts & 2) ? chunk : 0);
+  const long long items = parts == 1 ? n_ent : chunk;
   if (items <= 0) return FBN_OK;
-  // the window-only pass runs beside the step: a few workgroups per CU leave the CUs' wave
-  // slots to the main stream while its four-chain replay keeps the VALU busy
-  static const int wcap = getenv("FBN_WINDOW_BLOCKS") ? atoi(getenv("FBN_WINDOW_BLOCKS")) : 256;
-  const long long cap = parts == 2 ? wcap : 8192;
   if (pend && (!ring || !coef_hist || ring_n <= F)) {
     fbn_set_error("fbn_adam_catchup: deferred gradients need ring, coef_hist and ring_n > F");
     return FBN_ERR_ARG;
   }
   const PendSrc ps = make_pend(pend, ring, coef_hist, ring_stride, ring_n);
-  // the window alone: the replay engine over FBN_WIN_ROWS rows per wave (FBN_WINDOW_ONEPASS=1 keeps
-  // adam_catchup_kernel, A/B)
-  static const bool wone = getenv("FBN_WINDOW_ONEPASS") && atoi(getenv("FBN_WINDOW_ONEPASS")) == 1;
-  if (parts == 2 && !wone) {
-    // rows per wave: 16 below d = 128 (one round of the narrow engine); wave-wide rows take fewer
-    // (FBN_WIN_RPW, default 8) so more waves replay side by side
-    const char* we = getenv("FBN_WIN_RPW");
-    const int wr = we ? std::max(1, std::min(64, atoi(we))) : 8;
-    const int rpw = D >= 128 ? wr : FBN_WIN_ROWS;
-    long long waves = (chunk + rpw - 1) / rpw;
-    const char* wc = getenv("FBN_WIN_WAVES");   // cap on the grid's waves (A/B knob; 0 = none)
-    if (wc && atoll(wc) > 0) waves = std::min(waves, atoll(wc));
+  if (parts == 2) {
+    // the window runs beside the step, on the replay engine.  Rows per wave: 16 below d = 128 (one
+    // round of the narrow engine); wave-wide rows take 8, so more waves replay side by side
+    const int rpw = D >= 128 ? 8 : FBN_WIN_ROWS;
+    const long long waves = (chunk + rpw - 1) / rpw;
     const dim3 g2((unsigned)((waves + 3) / 4));
-    const char* ge = getenv("FBN_WIN_G");   // rows per replay group (4, or 2; A/B knob)
-    if (D >= 128 && ge && atoi(ge) == 2) {
-#define FBN_WIN2_G2(DW_)                                                                                       \
-  if (D == 128)                                                                                                \
-    fbn_launch((adam_window2_kernel<128, DW_, 2>), g2, dim3(256), 0, st, p, m, v, map, nrows, F, chunk, \
-                       last, (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps, rpw);             \
-  else                                                                                                         \
-    fbn_launch((adam_window2_kernel<256, DW_, 2>), g2, dim3(256), 0, st, p, m, v, map, nrows, F, chunk, \
-                       last, (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps, rpw);
-      if (decoupled) {
-        FBN_WIN2_G2(true)
-      } else {
-        FBN_WIN2_G2(false)
-      }
-#undef FBN_WIN2_G2
-      FBN_CHECK_LAUNCH();
-      return FBN_OK;
-    }
     if (decoupled) {
       FBN_DISPATCH_D_B(adam_window2_kernel, true, D, g2, p, m, v, map, nrows, F, chunk, last,
                        (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps, rpw);
@@ -2815,16 +2727,15 @@ extern "C" int fbn_adam_catchup(float* p, float* m, float* v, long long nrows, i
     FBN_CHECK_LAUNCH();
     return FBN_OK;
   }
-  // one wave per SCAN items (16 at D >= 64, else 64; sorted and compacted inside the kernel)
+  // one wave per SCAN entries (16 at D >= 64, else 64; sorted and compacted inside the kernel)
   const long long scan = D >= 64 ? 16 : 64;
-  const dim3 grid((unsigned)std::min<long long>(cap, (items + 4 * scan - 1) / (4 * scan)));
-  const ClaimSrc cs{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const dim3 grid((unsigned)std::min<long long>(8192, (items + 4 * scan - 1) / (4 * scan)));
   if (decoupled) {
-    FBN_DISPATCH_D_B(adam_catchup_kernel, true, D, grid, p, m, v, slot_row, n_ent, map, nrows, F, chunk, parts, last,
-                     (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps, cs);
+    FBN_DISPATCH_D_B(adam_catchup_kernel, true, D, grid, p, m, v, slot_row, n_ent, F, last,
+                     (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps);
   } else {
-    FBN_DISPATCH_D_B(adam_catchup_kernel, false, D, grid, p, m, v, slot_row, n_ent, map, nrows, F, chunk, parts, last,
-                     (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps, cs);
+    FBN_DISPATCH_D_B(adam_catchup_kernel, false, D, grid, p, m, v, slot_row, n_ent, F, last,
+                     (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps);
   }
   FBN_CHECK_LAUNCH();
   return FBN_OK;
@@ -2856,11 +2767,9 @@ static int launch_prefetch_binned(const ClaimSrc& cs, long long n, float* p, flo
   const int nblk = (int)((n + 255) / 256);
   fbn_launch(pfb_zero_kernel, dim3(1), dim3(256), 0, st, counts);
   fbn_launch(adam_pretag_kernel, dim3((unsigned)((n + FBN_PRETAG_BLOCK - 1) / FBN_PRETAG_BLOCK)),
-             dim3(FBN_PRETAG_BLOCK), 0, st, cs, (int)n, step, pretag_flat());
+             dim3(FBN_PRETAG_BLOCK), 0, st, cs, (int)n, step);
   fbn_launch(adam_pfbin_kernel, dim3(nblk), dim3(256), 0, st, cs, (int)n, last, step, ps, counts, recs);
-  // FBN_PFB_CHUNK: records per replay wave (A/B knob, read per call; 1 .. 64)
-  const char* ce = getenv("FBN_PFB_CHUNK");
-  const int ch = ce ? std::max(1, std::min(64, atoi(ce))) : 32;
+  const int ch = 32;   // records per replay wave (see adam_pfreplay_kernel)
   // at most one chunk per ch records plus one partial chunk per list
   const long long waves = (n + ch - 1) / ch + FBN_PFB_NB * FBN_PFB_NC;
   const dim3 g((unsigned)((waves + 3) / 4));
@@ -2924,62 +2833,14 @@ extern "C" int fbn_adam_prefetch(const int64_t* item, const int64_t* seq, int B,
   const float omb2 = (float)(1.0 - (double)beta2);
   const PendSrc ps = make_pend(pend, ring, coef_hist, ring_stride, ring_n);
   const ClaimSrc cs{item, L > 0 ? seq : nullptr, L, V, const_cast<int*>(map), nullptr, nullptr, nullptr, preclaim};
-  static const int pcap = getenv("FBN_PREFETCH_BLOCKS") ? atoi(getenv("FBN_PREFETCH_BLOCKS")) : 256;
-  const dim3 grid((unsigned)std::min<long long>(pcap, (n + 63) / 64));
   hipStream_t st = (hipStream_t)stream;
-  // with pre-claims: the two-pass form (FBN_PREFETCH_ONEPASS=1 keeps the one-pass kernel, A/B)
-  static const bool onepass = getenv("FBN_PREFETCH_ONEPASS") && atoi(getenv("FBN_PREFETCH_ONEPASS")) == 1;
-  if (preclaim && (!onepass || D < 128)) {
-    const dim3 g2((unsigned)((n + 255) / 256));
+  if (preclaim) {   // with pre-claims: the two-pass form
     fbn_launch(adam_pretag_kernel, dim3((unsigned)((n + FBN_PRETAG_BLOCK - 1) / FBN_PRETAG_BLOCK)),
-               dim3(FBN_PRETAG_BLOCK), 0, st, cs, (int)n, step, pretag_flat());
+               dim3(FBN_PRETAG_BLOCK), 0, st, cs, (int)n, step);
     FBN_CHECK_LAUNCH();
-    const char* ee = getenv("FBN_PF_EPW");   // A/B knob, read per call (tools/ab_step.py flips it in-process)
-    const int epw = ee ? std::max(1, std::min(64, atoi(ee))) : 64;
-    // FBN_PF_WAVES: cap on the grid's waves (0 = one wave per entry chunk); A/B knob
-    const char* wc = getenv("FBN_PF_WAVES");
-    long long waves = (n + epw - 1) / epw;
-    if (wc && atoll(wc) > 0) waves = std::min(waves, atoll(wc));
+    const int epw = 64;   // entries per wave
+    const long long waves = (n + epw - 1) / epw;
     const dim3 g3((unsigned)((waves + 3) / 4));   // 4 waves per block
-    // FBN_PF_ABL (measurement only, tools/pf_ablation.py; 1 and 2 are NOT a valid Adam step):
-    // 1 = the replay without its arithmetic, 2 = without its row traffic; 3 = groups of 8 rows
-    // (valid), 4 = groups of 8 without row traffic
-    const char* ab = getenv("FBN_PF_ABL");
-    if (D == 128 && !decoupled && ab && (atoi(ab) == 1 || atoi(ab) == 2 || atoi(ab) == 3 || atoi(ab) == 4)) {
-      if (atoi(ab) == 3)   // groups of 8 rows (diagnosis: more independent update chains per wave)
-        fbn_launch((adam_prefetch2_kernel<128, false, 8, 0>), g3, dim3(256), 0, st, p, m, v, cs, (int)n,
-                           last, (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps, epw);
-      else if (atoi(ab) == 4)   // groups of 8 rows without row traffic
-        fbn_launch((adam_prefetch2_kernel<128, false, 8, 2>), g3, dim3(256), 0, st, p, m, v, cs, (int)n,
-                           last, (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps, epw);
-      else if (atoi(ab) == 1)
-        fbn_launch((adam_prefetch2_kernel<128, false, 4, 1>), g3, dim3(256), 0, st, p, m, v, cs, (int)n,
-                           last, (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps, epw);
-      else
-        fbn_launch((adam_prefetch2_kernel<128, false, 4, 2>), g3, dim3(256), 0, st, p, m, v, cs, (int)n,
-                           last, (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps, epw);
-      FBN_CHECK_LAUNCH();
-      return FBN_OK;
-    }
-    // FBN_PF_G: rows per replay group (4, or 2 for half the register footprint; A/B knob)
-    const char* ge = getenv("FBN_PF_G");
-    if (D >= 128 && ge && atoi(ge) == 2) {
-#define FBN_PF2_G2(DW_)                                                                                        \
-  if (D == 128)                                                                                                \
-    fbn_launch((adam_prefetch2_kernel<128, DW_, 2>), g3, dim3(256), 0, st, p, m, v, cs, (int)n, last, \
-                       (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps, epw);                  \
-  else                                                                                                         \
-    fbn_launch((adam_prefetch2_kernel<256, DW_, 2>), g3, dim3(256), 0, st, p, m, v, cs, (int)n, last, \
-                       (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps, epw);
-      if (decoupled) {
-        FBN_PF2_G2(true)
-      } else {
-        FBN_PF2_G2(false)
-      }
-#undef FBN_PF2_G2
-      FBN_CHECK_LAUNCH();
-      return FBN_OK;
-    }
     if (decoupled) {
       FBN_DISPATCH_D_B(adam_prefetch2_kernel, true, D, g3, p, m, v, cs, (int)n, last, (const AdamConsts*)consts_table,
                        step, wd, beta2, omb2, eps, ps, epw);
@@ -2990,6 +2851,7 @@ extern "C" int fbn_adam_prefetch(const int64_t* item, const int64_t* seq, int B,
     FBN_CHECK_LAUNCH();
     return FBN_OK;
   }
+  const dim3 grid((unsigned)std::min<long long>(256, (n + 63) / 64));   // D >= 128 without pre-claims: one pass
   if (D == 128) {
     if (decoupled)
       fbn_launch((adam_prefetch_kernel<128, true>), grid, dim3(256), 0, st, p, m, v, cs, (int)n, last,
@@ -3038,7 +2900,7 @@ extern "C" int fbn_adam_prefetch_rows(const int* lids, int n, int skip0, long lo
     cs.pre = preclaim;
     const dim3 g2((unsigned)((n + 255) / 256));
     fbn_launch(adam_pretag_kernel, dim3((unsigned)((n + FBN_PRETAG_BLOCK - 1) / FBN_PRETAG_BLOCK)),
-               dim3(FBN_PRETAG_BLOCK), 0, st, cs, n, step, pretag_flat());
+               dim3(FBN_PRETAG_BLOCK), 0, st, cs, n, step);
     const int epw = 64;
     const dim3 g3((unsigned)(((n + epw - 1) / epw + 3) / 4));
     if (decoupled) {
@@ -3051,8 +2913,7 @@ extern "C" int fbn_adam_prefetch_rows(const int* lids, int n, int skip0, long lo
     FBN_CHECK_LAUNCH();
     return FBN_OK;
   }
-  static const int pcap = getenv("FBN_PREFETCH_BLOCKS") ? atoi(getenv("FBN_PREFETCH_BLOCKS")) : 256;
-  const dim3 grid((unsigned)std::min<long long>(pcap, ((long long)n + 63) / 64));
+  const dim3 grid((unsigned)std::min<long long>(256, ((long long)n + 63) / 64));
   if (D == 128) {
     if (decoupled)
       fbn_launch((adam_prefetch_kernel<128, true>), grid, dim3(256), 0, st, p, m, v, cs, n, last,
@@ -3172,13 +3033,10 @@ static int claim_catchup_impl(const int64_t* item, const int64_t* seq, int B, in
   }
   hipStream_t st = (hipStream_t)stream;
   const float omb2 = (float)(1.0 - (double)beta2);
-  const long long chunk = (nrows + F - 1) / F;
   const PendSrc ps = make_pend(pend, ring, coef_hist, ring_stride, ring_n);
   const ClaimSrc cs{item, L > 0 ? seq : nullptr, L, V, map, slot_row, dup, hasdup, preclaim};
-  // one entry per lane, row state in one round trip, the replay engine (adam_claim2_kernel);
-  // FBN_CLAIM_ONEPASS=1 keeps the scans of adam_catchup_kernel (A/B)
-  static const bool cone = getenv("FBN_CLAIM_ONEPASS") && atoi(getenv("FBN_CLAIM_ONEPASS")) == 1;
-  if (conv_tiles > 0 && !cone) {
+  // one entry per lane, row state in one round trip, the replay engine (adam_claim2_kernel)
+  if (conv_tiles > 0) {
     const int nclaim = (int)((n + 255) / 256);
     const dim3 g2((unsigned)(nclaim + conv_tiles));
     if (decoupled) {
@@ -3191,30 +3049,13 @@ static int claim_catchup_impl(const int64_t* item, const int64_t* seq, int B, in
     FBN_CHECK_LAUNCH();
     return FBN_OK;
   }
-  if (conv_tiles > 0) {   // FBN_CLAIM_ONEPASS: the images in their own launch first
-    fbn_launch(convert_bf16_kernel_o, dim3(conv_tiles), dim3(256), 0, st, cj, n_conv);
-    FBN_CHECK_LAUNCH();
-  }
-  if (!cone) {
-    const dim3 g2((unsigned)((n + 255) / 256));
-    if (decoupled) {
-      FBN_DISPATCH_D_B(adam_claim2_kernel, true, D, g2, p, m, v, cs, (int)n, last, (const AdamConsts*)consts_table,
-                       step, wd, beta2, omb2, eps, ps);
-    } else {
-      FBN_DISPATCH_D_B(adam_claim2_kernel, false, D, g2, p, m, v, cs, (int)n, last, (const AdamConsts*)consts_table,
-                       step, wd, beta2, omb2, eps, ps);
-    }
-    FBN_CHECK_LAUNCH();
-    return FBN_OK;
-  }
-  const long long scan = D >= 64 ? 16 : 64;
-  const dim3 grid((unsigned)std::min<long long>(8192, (n + 4 * scan - 1) / (4 * scan)));
+  const dim3 g2((unsigned)((n + 255) / 256));
   if (decoupled) {
-    FBN_DISPATCH_D_B(adam_catchup_kernel, true, D, grid, p, m, v, slot_row, (int)n, map, nrows, F, chunk, 1, last,
-                     (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps, cs);
+    FBN_DISPATCH_D_B(adam_claim2_kernel, true, D, g2, p, m, v, cs, (int)n, last, (const AdamConsts*)consts_table,
+                     step, wd, beta2, omb2, eps, ps);
   } else {
-    FBN_DISPATCH_D_B(adam_catchup_kernel, false, D, grid, p, m, v, slot_row, (int)n, map, nrows, F, chunk, 1, last,
-                     (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps, cs);
+    FBN_DISPATCH_D_B(adam_claim2_kernel, false, D, g2, p, m, v, cs, (int)n, last, (const AdamConsts*)consts_table,
+                     step, wd, beta2, omb2, eps, ps);
   }
   FBN_CHECK_LAUNCH();
   return FBN_OK;

@@ -85,20 +85,13 @@ int call_op(const Op& o) { return o.fn(o.i, o.f); }
 
 // The program's events only order work between streams of one device, so their release need not be
 // system scope (the default: an L2 writeback + invalidate at every record, ~6 us of idle on the
-// recording stream before its next kernel).  FBN_PLAN_EVENT_SCOPE (A/B knob, read at event creation):
-// "device" (default) -- hipEventDisableSystemFence; "release_device" -- hipEventReleaseToDevice;
-// "system" -- the runtime's default fence.
-unsigned event_flags() {
-  const char* e = getenv("FBN_PLAN_EVENT_SCOPE");
-  if (e && !strcmp(e, "system")) return hipEventDisableTiming;
-  if (e && !strcmp(e, "release_device")) return hipEventDisableTiming | hipEventReleaseToDevice;
-  return hipEventDisableTiming | hipEventDisableSystemFence;
-}
+// recording stream before its next kernel).
+constexpr unsigned kEventFlags = hipEventDisableTiming | hipEventDisableSystemFence;
 
 int ensure_event(Plan* p, int slot) {
   while ((int)p->events.size() <= slot) {
     hipEvent_t e;
-    if (hipEventCreateWithFlags(&e, event_flags()) != hipSuccess) {
+    if (hipEventCreateWithFlags(&e, kEventFlags) != hipSuccess) {
       fbn_set_error("fbn_plan: hipEventCreateWithFlags failed");
       return 2;
     }

@@ -377,7 +377,8 @@ int fbn_adam_touched(float* p, float* m, float* v, int D, int* map, const float*
  * Replaces the per-step dense Adam pass of torch.optim.Adam over item_emb.weight
  * (src/train_fibinet.py:78,121) by O(touched + nrows/F) rows per step.  F <= 512. */
 /* parts: 1 = claimed rows (before the gather), 2 = rolling window (unclaimed rows; may overlap the
- * step on another stream), 3 = both. */
+ * step on another stream), one launch each; any other value (3 = both included: it has no caller)
+ * returns FBN_ERR_ARG, checked on the host before any device work. */
 /* Deferred gradients (single GPU; pend == NULL disables): pend[r] = index b*2+slot of the
  * per-sample gradient vector row r received at step last[r] (-1 = none); ring [ring_n][B][2][D]
  * holds step s's vectors in slot s % ring_n (ring_stride = B*2*D floats, ring_n > F);

@@ -35,6 +35,40 @@ def test_workspace_queries_are_host_only():
     assert h.fbn_bn_workspace_size(8192, 512) > 0
 
 
+def test_adam_catchup_rejects_both_parts_on_the_host():
+    """fbn_adam_catchup takes parts = 1 (claimed rows) or 2 (rolling window), one launch each;
+    parts = 3 is refused by the argument check, which precedes any device call (null pointers and
+    no GPU here)."""
+    from ctr_recommendation_amd import _lib
+    h = _lib.lib()
+    rc = h.fbn_adam_catchup(None, None, None, 1, 128, None, 0, None, 1, 3, None, None, None, 0.0, 0.999, 1e-8,
+                            None, None, None, 0, 0, 0, None)
+    assert rc == 1   # FBN_ERR_ARG
+    assert b"parts" in h.fbn_last_error()
+
+
+def test_library_reads_only_documented_environment():
+    """What the environment can change in the native library is written down: the FBN_* names the
+    sources pass to getenv are either in INTEGRATION.md's table (and in the product library) or
+    compiled into a tuning variant only (and absent from the product library)."""
+    csrc = os.path.join(ROOT, "ctr_recommendation_amd", "csrc")
+    read = set()
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".cpp", ".h")):
+            read |= set(re.findall(r'getenv\(\s*"(FBN_[A-Z0-9_]+)"', open(os.path.join(csrc, f)).read()))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = doc.split("Environment variables the native library reads", 1)[1]
+    documented = set(re.findall(r"^\| `(FBN_[A-Z0-9_]+)` \|", section, flags=re.M))
+    lib = open(os.path.join(ROOT, "ctr_recommendation_amd", "libfibinet_hip.so"), "rb").read()
+    for name in sorted(documented):
+        assert name.encode() + b"\0" in lib, f"{name} is documented but the library does not read it"
+    for name in sorted(read - documented):
+        assert name.encode() not in lib, f"{name} is read by the product library but not documented"
+    assert documented <= read
+    assert documented == {"FBN_BN_ACT_R4", "FBN_BN_REDUCE_NC", "FBN_FIELDS_CMP", "FBN_FIELDS_HCH",
+                          "FBN_GROUP_SPLIT_DIV", "FBN_GROUP_W4"}
+
+
 def test_wgrad_group_split_fills_two_workgroups_per_cu(monkeypatch):
     """The grouped weight-gradient launch's K-slabs (host planning only): by default 3/4 of the
     single launches' slabs, rounded, so C3's four problems (dWa 512 x 1920, dWb 256 x 512, the

@@ -2,8 +2,8 @@
 ops), alternating blocks of K steps per arm for R rounds on one trainer at steady state; prints
 the median ms/step per arm (AB_ZIPF=s: Zipf(s) ids).  Usage: python tools/ab_step.py ARM [ARM ...] with ARM =
 name:module.GLOBAL=value[;module.GLOBAL=value...] ('base' = no change; module env = an
-environment variable the library reads per call), e.g.
-  python tools/ab_step.py base claim_main:trainer._CLAIM_ON_SIDE=False"""
+environment variable the library reads per call: the table in INTEGRATION.md lists them), e.g.
+  python tools/ab_step.py base claim_main:trainer._CLAIM_ON_SIDE=False w4:env.FBN_GROUP_W4=1"""
 import os
 import sys
 import time

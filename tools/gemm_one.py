@@ -1,7 +1,8 @@
 """Run one C3 bf16 GEMM shape ITER times (a target for rocprofv3 --pmc / --kernel-trace passes).
 
   python tools/gemm_one.py NAME [ITER]      NAME: F3 | F4 | dh1 | dc | U | dWa | dW4
-FBN_GEMM_FORCE="bm,bn,split[,waves[,stages]]" forces a plan (see gemm_sweep.py).
+FBN_GEMM_FORCE="bm,bn,split[,waves[,stages]]" forces a plan (see gemm_sweep.py, which builds and
+selects the "sweep" variant of the library that reads it).
 """
 import os
 import sys
@@ -9,8 +10,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from ctr_recommendation_amd import ops
-from gemm_sweep import SH, operands  # noqa: E402  (tools/ is on sys.path as the script dir)
+from gemm_sweep import SH, operands  # noqa: E402  (tools/ is on sys.path as the script dir; selects the variant)
+from ctr_recommendation_amd import ops  # noqa: E402
 
 
 def main():

@@ -1,7 +1,9 @@
 """Time fbn_gemm on the C3 bf16 shapes under forced tile / split-K plans (tuning aid).
 
   python tools/gemm_sweep.py [name-filter ...]
-FBN_GEMM_FORCE="bm,bn,split" forces a plan; FBN_GEMM_NO_DMA16=1 disables the LDS-DMA NT kernel.
+FBN_GEMM_FORCE="bm,bn,split" forces a plan; FBN_GEMM_NO_DMA16=1 disables the LDS-DMA NT kernel.  Only
+the "sweep" variant of the library (build.py VARIANTS) reads these two: it is built here and loaded
+through FBN_LIB_PATH, the product library ignores them.
 Every timed configuration is also checked against torch (fp32 accumulate of the bf16 operands).
 """
 import os
@@ -10,7 +12,10 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from ctr_recommendation_amd import ops
+from ctr_recommendation_amd.build import build_variant
+
+os.environ.setdefault("FBN_LIB_PATH", build_variant("sweep"))   # before _lib reads it
+from ctr_recommendation_amd import ops  # noqa: E402
 
 dev = "cuda"
 bf = torch.bfloat16

@@ -6,7 +6,7 @@ Arms (interleaved in one process, ROUNDS rounds; each arm sets environment knobs
 per call), e.g.
     python tools/time_fields.py "plain:" "cmp10:FBN_FIELDS_CMP=1,FBN_FIELDS_HCH=10"
 Knobs: FBN_FIELDS_HCH the history rows in flight per chunk, FBN_FIELDS_CMP=1 live slots compacted
-first, FBN_FIELDS_NOBUF=1 global loads instead of the buffer resource, FBN_GATHER_HOT=<tau> hot-row LDS staging; env ZIPF=<s> draws Zipf(s) ids, D / B the shape."""
+first, FBN_GATHER_HOT=<tau> hot-row LDS staging; env ZIPF=<s> draws Zipf(s) ids, D / B the shape."""
 import os
 import sys
 
