@@ -141,6 +141,11 @@ SIGNATURES = {
     "fbn_eval_pack": (I, [P, P, LL, P, P, P]),
     "fbn_eval_workspace_size": (SZ, [LL]),
     "fbn_eval_reduce": (I, [P, LL, P, SZ, P, P, P]),
+    "fbn_rec_item_cache": (I, [P, P, P, P, P, P, F, I, LL, P, P, I, I, P]),
+    "fbn_rec_hist_pool": (I, [P, P, LL, P, P, I, I, I, P]),
+    "fbn_rec_fields": (I, [P, P, P, P, P, P, I, P, LL, P, P, P, P, I, P, P, P, I, I, P, P, I, I, I, I, P]),
+    "fbn_rec_topk_workspace_size": (SZ, [I, I, I]),
+    "fbn_rec_topk": (I, [P, I, I, I, P, P, I, I, I, P, P, SZ, P, P, P, P, P, P]),
     "fbn_plan_create": (I, [P]),
     "fbn_plan_destroy": (I, [P]),
     "fbn_plan_size": (I, [P]),

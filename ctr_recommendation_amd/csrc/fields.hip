@@ -18,9 +18,8 @@
 // Small parameter gradients (SENET, LN, cate table) are reduced per block in LDS and
 // written as per-block partial slabs summed by fbn_reduce_partials (deterministic).
 #include "common.h"
+#include "fields_common.h"   // FBN_MAXR, FBN_MAX_L, ln_relu, senet_excite (shared with recommend.hip)
 
-#define FBN_MAXR 8   // max SENET reduced width supported (reference: 3)
-#define FBN_MAX_L 32 // max history length (the reference keeps the last 20)
 #ifndef FBN_HCH
 // default history rows in flight per sample before they are summed (FBN_FIELDS_HCH: 5 / 10 / 20;
 // the sum runs in slot order whatever the chunk, so every choice gives the same bits): 10 -- round 3
@@ -76,42 +75,6 @@ __device__ __forceinline__ void map_claim(int* map, int* slot_row, int r, int e)
   if (__hip_atomic_compare_exchange_strong(map + r, &expected, e, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_AGENT))
     slot_row[e] = r;
-}
-
-// field 4 = ReLU(LayerNorm(h)) for this lane's 4 columns; shared by the forward and the
-// backward's recompute so both run the same operations (bit-identical)
-template <int G>
-__device__ __forceinline__ f32x4 ln_relu(const f32x4& h, const float* ln_g, const float* ln_b, float eps, int q) {
-  constexpr int D = 4 * G;
-  const float s1 = group_sum<G>(h[0] + h[1] + h[2] + h[3]);
-  const float mean = s1 / (float)D;
-  const f32x4 dh = h - mean;
-  const float s2 = group_sum<G>(dh[0] * dh[0] + dh[1] * dh[1] + dh[2] * dh[2] + dh[3] * dh[3]);
-  const float rstd = 1.f / sqrtf(s2 / (float)D + eps);
-  const f32x4 g4 = *reinterpret_cast<const f32x4*>(ln_g + 4 * q);
-  const f32x4 bb4 = *reinterpret_cast<const f32x4*>(ln_b + 4 * q);
-  f32x4 x4;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) x4[e] = fmaxf(dh[e] * rstd * g4[e] + bb4[e], 0.f);
-  return x4;
-}
-
-template <int D>
-__device__ __forceinline__ void senet_excite(const float (&z)[6], const float* w1, const float* b1,
-                                             const float* w2, const float* b2, int R, float (&q)[FBN_MAXR],
-                                             float (&a)[6]) {
-  for (int j = 0; j < R; ++j) {
-    float s = b1[j];
-#pragma unroll
-    for (int f = 0; f < 6; ++f) s += w1[j * 6 + f] * z[f];
-    q[j] = s;
-  }
-#pragma unroll
-  for (int f = 0; f < 6; ++f) {
-    float s = b2[f];
-    for (int j = 0; j < R; ++j) s += w2[f * R + j] * fmaxf(q[j], 0.f);
-    a[f] = 1.f / (1.f + __expf(-s));
-  }
 }
 
 // row r of the exchanged row buffer (MODE 1: f32 rows; MODE 2: bf16 rows, the bf16 mode's wire format)

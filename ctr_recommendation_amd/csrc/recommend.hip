@@ -1,0 +1,427 @@
+// Serving: score a catalogue of M items for U users and keep each user's K best on the device.
+//
+// The training forward (fields.hip) builds the five fields of every batch row from scratch: 21 table
+// rows per row, and the mm projection's LayerNorm.  Scoring U x M (user, candidate) pairs through it
+// repeats work that depends on one side only, so the pair's fields are composed from two caches:
+//   per candidate m (fbn_rec_item_cache, once per catalogue):  X4[m] = ReLU(LN(hmm[m]))
+//   per user u      (fbn_rec_hist_pool, once per call):        X5[u] = masked mean of E[seq[u]]
+//   per pair        (fbn_rec_fields):  X1 = C[likes[m]], X2 = C[views[m]], X3 = E[item[m]] (contiguous
+//                   over a run of candidates), X4[m], X5[u] (one L2-resident row), then SENET -- the same
+//                   device functions in the same order as fields_fwd_kernel (fields_common.h), so the
+//                   operands handed to the bilinear / MLP kernels are the same bits.
+// fbn_rec_topk turns a chunk's logits into 64-bit keys {ordered logit, ~catalogue position} and keeps
+// each user's K largest across chunks: integer compares only, no float atomics, no sort of U x M.
+#include "common.h"
+#include "fields_common.h"
+
+static bool rec_dim_ok(int D) { return D == 16 || D == 32 || D == 64 || D == 128 || D == 256; }
+
+// workgroups of 256 threads for `rows` rows of D/4 lanes each (grid-stride beyond the cap)
+static int rec_grid(long long rows, int D) {
+  const int spw = 64 / (D / 4);
+  const long long waves = (rows + spw - 1) / spw;
+  const long long blocks = (waves + 3) / 4;
+  return blocks < 1 ? 1 : (blocks > 4096 ? 4096 : (int)blocks);
+}
+
+// ------------------------------------------------------------------------------ item-side cache
+struct RecItemArgs {
+  const int64_t* item_id; const int64_t* likes; const int64_t* views;   // [M]
+  const float* hmm;          // [M][D] pre-LayerNorm mm projection (bias included)
+  const float* ln_g; const float* ln_b;
+  float* cache;              // [M][D] field 4
+  int* err;
+  long long V;
+  int M, n_cate;
+  float ln_eps;
+};
+
+template <int D>
+__global__ void __launch_bounds__(256) rec_item_cache_kernel(RecItemArgs p) {
+  constexpr int G = D / 4, SPW = 64 / G;
+  const int lane = threadIdx.x & 63, q = lane % G;
+  const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int nwaves = (gridDim.x * blockDim.x) >> 6;
+  for (long long m0 = (long long)gw * SPW; m0 < p.M; m0 += (long long)nwaves * SPW) {
+    const long long m = m0 + lane / G;
+    if (m >= p.M) continue;
+    const long long item = p.item_id[m], lk = p.likes[m], vw = p.views[m];
+    if (item < 0 || item >= p.V || lk < 0 || lk >= p.n_cate || vw < 0 || vw >= p.n_cate) atomicOr(p.err, 1);
+    const f32x4 h = *reinterpret_cast<const f32x4*>(p.hmm + m * D + 4 * q);
+    *reinterpret_cast<f32x4*>(p.cache + m * D + 4 * q) = ln_relu<G>(h, p.ln_g, p.ln_b, p.ln_eps, q);
+  }
+}
+
+extern "C" int fbn_rec_item_cache(const int64_t* item_id, const int64_t* likes, const int64_t* views,
+                                  const float* hmm, const float* ln_g, const float* ln_b, float ln_eps, int n_cate,
+                                  long long V, float* cache, int* err, int M, int D, void* stream) {
+  if (!rec_dim_ok(D)) {
+    fbn_set_error("fbn_rec_item_cache: embedding_dim D must be one of 16,32,64,128,256");
+    return FBN_ERR_ARG;
+  }
+  if (M <= 0) return FBN_OK;
+  RecItemArgs a;
+  a.item_id = item_id; a.likes = likes; a.views = views; a.hmm = hmm; a.ln_g = ln_g; a.ln_b = ln_b;
+  a.cache = cache; a.err = err; a.V = V; a.M = M; a.n_cate = n_cate; a.ln_eps = ln_eps;
+  const dim3 grid(rec_grid(M, D)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  switch (D) {
+    case 16: fbn_launch(rec_item_cache_kernel<16>, grid, block, 0, st, a); break;
+    case 32: fbn_launch(rec_item_cache_kernel<32>, grid, block, 0, st, a); break;
+    case 64: fbn_launch(rec_item_cache_kernel<64>, grid, block, 0, st, a); break;
+    case 128: fbn_launch(rec_item_cache_kernel<128>, grid, block, 0, st, a); break;
+    default: fbn_launch(rec_item_cache_kernel<256>, grid, block, 0, st, a); break;
+  }
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}
+
+// ------------------------------------------------------------------------------ user-side pooling
+struct RecHistArgs {
+  const int64_t* item_seq;   // [U][L] or null (zero rows)
+  const float* table;        // [V][D]
+  float* hist;               // [U][D]
+  int* err;
+  long long V;
+  int U, L;
+};
+
+#define REC_HCH 8   // history rows in flight per user before they are summed (slot order whatever the chunk)
+
+template <int D>
+__global__ void __launch_bounds__(256) rec_hist_pool_kernel(RecHistArgs p) {
+  constexpr int G = D / 4, SPW = 64 / G;
+  const int lane = threadIdx.x & 63, q = lane % G;
+  const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int nwaves = (gridDim.x * blockDim.x) >> 6;
+  const int L = p.item_seq ? p.L : 0;
+  for (int u0 = gw * SPW; u0 < p.U; u0 += nwaves * SPW) {
+    const int u = u0 + lane / G;
+    if (u >= p.U) continue;
+    f32x4 hs = {0.f, 0.f, 0.f, 0.f};
+    int nnz = 0;
+    bool bad = false;
+    for (int t0 = 0; t0 < L; t0 += REC_HCH) {
+      // branch-free: a padding or past-L slot reads row 0 and contributes +0 by a select
+      f32x4 rows[REC_HCH];
+      bool live[REC_HCH];
+#pragma unroll
+      for (int k = 0; k < REC_HCH; ++k) {
+        const int t = t0 + k;
+        long long s = t < L ? p.item_seq[(size_t)u * L + t] : 0;
+        if (s < 0 || s >= p.V) { bad = true; s = 0; }
+        live[k] = s != 0;
+        rows[k] = *reinterpret_cast<const f32x4*>(p.table + s * D + 4 * q);
+      }
+#pragma unroll
+      for (int k = 0; k < REC_HCH; ++k) {
+        hs += live[k] ? rows[k] : (f32x4){0.f, 0.f, 0.f, 0.f};
+        nnz += live[k] ? 1 : 0;
+      }
+    }
+    if (bad) atomicOr(p.err, 1);
+    const float cnt = fmaxf((float)nnz, 1.f);
+    *reinterpret_cast<f32x4*>(p.hist + (size_t)u * D + 4 * q) = hs / cnt;
+  }
+}
+
+extern "C" int fbn_rec_hist_pool(const int64_t* item_seq, const float* table, long long V, float* hist, int* err,
+                                 int U, int L, int D, void* stream) {
+  if (!rec_dim_ok(D)) {
+    fbn_set_error("fbn_rec_hist_pool: embedding_dim D must be one of 16,32,64,128,256");
+    return FBN_ERR_ARG;
+  }
+  if (L < 0 || L > FBN_MAX_L) {
+    fbn_set_error("fbn_rec_hist_pool: history length L must be in 0..32");
+    return FBN_ERR_ARG;
+  }
+  if (U <= 0) return FBN_OK;
+  RecHistArgs a;
+  a.item_seq = L > 0 ? item_seq : nullptr; a.table = table; a.hist = hist; a.err = err; a.V = V; a.U = U; a.L = L;
+  const dim3 grid(rec_grid(U, D)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  switch (D) {
+    case 16: fbn_launch(rec_hist_pool_kernel<16>, grid, block, 0, st, a); break;
+    case 32: fbn_launch(rec_hist_pool_kernel<32>, grid, block, 0, st, a); break;
+    case 64: fbn_launch(rec_hist_pool_kernel<64>, grid, block, 0, st, a); break;
+    case 128: fbn_launch(rec_hist_pool_kernel<128>, grid, block, 0, st, a); break;
+    default: fbn_launch(rec_hist_pool_kernel<256>, grid, block, 0, st, a); break;
+  }
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}
+
+// ------------------------------------------------------------------------------ pair composition + SENET
+struct RecFieldArgs {
+  const int64_t* item_id; const int64_t* likes; const int64_t* views;   // [M] catalogue columns
+  const float* cache;        // [M][D] field 4 (fbn_rec_item_cache)
+  const float* hist;         // [U][D] field 5 (fbn_rec_hist_pool)
+  const float* cate;         // [n_cate][D]
+  const float* table;        // [V][D]
+  const float* w1; const float* b1; const float* w2; const float* b2;   // SENET [R][6],[R],[6][R],[6]
+  float* Vc;                 // [P][5][D] fields 1..5 after SENET (optional)
+  short* Vc16;               // bf16 copy (optional)
+  void* c;                   // [P][ldc] float or bf16 (c16): cols [0,5D) <- V (optional)
+  float* a_out;              // [P][6] (optional)
+  int* err;
+  long long V;
+  int U, m0, Mc, ldc, R, n_cate, c16;
+};
+
+template <int D>
+__global__ void __launch_bounds__(256) rec_fields_kernel(RecFieldArgs p) {
+  constexpr int G = D / 4, SPW = 64 / G;
+  const int lane = threadIdx.x & 63, q = lane % G;
+  const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int nwaves = (gridDim.x * blockDim.x) >> 6;
+  const long long P = (long long)p.U * p.Mc;
+  for (long long r0 = (long long)gw * SPW; r0 < P; r0 += (long long)nwaves * SPW) {
+    const long long b = r0 + lane / G;            // pair row u * Mc + (m - m0)
+    if (b >= P) continue;
+    const int u = (int)(b / p.Mc);
+    const long long m = p.m0 + (b - (long long)u * p.Mc);
+    // ---------------- ids (validated as fbn_fields_fwd does: a bad id reads row 0 / a zero row)
+    long long item = p.item_id[m], lk = p.likes[m], vw = p.views[m];
+    bool bad = false;
+    if (lk < 0 || lk >= p.n_cate) { bad = true; lk = 0; }
+    if (vw < 0 || vw >= p.n_cate) { bad = true; vw = 0; }
+    if (item < 0 || item >= p.V) { bad = true; item = -1; }
+    const f32x4 c1 = *reinterpret_cast<const f32x4*>(p.cate + lk * D + 4 * q);
+    const f32x4 c2 = *reinterpret_cast<const f32x4*>(p.cate + vw * D + 4 * q);
+    f32x4 rit = {0.f, 0.f, 0.f, 0.f};
+    if (item >= 0) rit = *reinterpret_cast<const f32x4*>(p.table + item * D + 4 * q);
+    const f32x4 x4 = *reinterpret_cast<const f32x4*>(p.cache + m * D + 4 * q);
+    const f32x4 x5 = *reinterpret_cast<const f32x4*>(p.hist + (size_t)u * D + 4 * q);
+    if (bad) atomicOr(p.err, 1);
+
+    // ---------------- SENET
+    const f32x4 xs[5] = {c1, c2, rit, x4, x5};
+    float z[6];
+    z[0] = 0.f;
+#pragma unroll
+    for (int f = 0; f < 5; ++f) z[f + 1] = group_sum<G>(xs[f][0] + xs[f][1] + xs[f][2] + xs[f][3]) / (float)D;
+    float qv[FBN_MAXR], a[6];
+    senet_excite<D>(z, p.w1, p.b1, p.w2, p.b2, p.R, qv, a);
+
+    // ---------------- stores
+    float* Vb = p.Vc ? p.Vc + (size_t)b * 5 * D + 4 * q : nullptr;
+    float* cb = (p.c && !p.c16) ? (float*)p.c + (size_t)b * p.ldc + 4 * q : nullptr;
+    short* cb16 = (p.c && p.c16) ? (short*)p.c + (size_t)b * p.ldc + 4 * q : nullptr;
+#pragma unroll
+    for (int f = 0; f < 5; ++f) {
+      const f32x4 v = xs[f] * a[f + 1];
+      if (p.Vc) *reinterpret_cast<f32x4*>(Vb + f * D) = v;
+      const bf16x4 v16 = (bf16x4){f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
+      if (cb16) *reinterpret_cast<bf16x4*>(cb16 + f * D) = v16;
+      else if (cb) *reinterpret_cast<f32x4*>(cb + f * D) = v;
+      if (p.Vc16) *reinterpret_cast<bf16x4*>(p.Vc16 + ((size_t)b * 5 + f) * D + 4 * q) = v16;
+    }
+    if (p.a_out) {
+#pragma unroll
+      for (int f = 0; f < 6; ++f)
+        if (f % G == q) p.a_out[(size_t)b * 6 + f] = a[f];   // G may be < 6 (D = 16)
+    }
+  }
+}
+
+extern "C" int fbn_rec_fields(const int64_t* item_id, const int64_t* likes, const int64_t* views, const float* cache,
+                              const float* hist, const float* cate, int n_cate, const float* table, long long V,
+                              const float* w1, const float* b1, const float* w2, const float* b2, int R, float* Vc,
+                              short* Vc16, void* c, int ldc, int c_bf16, float* a_out, int* err, int U, int m0, int Mc,
+                              int D, void* stream) {
+  if (!rec_dim_ok(D)) {
+    fbn_set_error("fbn_rec_fields: embedding_dim D must be one of 16,32,64,128,256");
+    return FBN_ERR_ARG;
+  }
+  if (R < 1 || R > FBN_MAXR || (ldc & 3) || m0 < 0) {
+    fbn_set_error("fbn_rec_fields: need 1 <= R <= 8, ldc % 4 == 0, m0 >= 0");
+    return FBN_ERR_ARG;
+  }
+  if (U <= 0 || Mc <= 0) return FBN_OK;
+  if ((long long)U * Mc > 0x7FFFFFFFll) {
+    fbn_set_error("fbn_rec_fields: U * Mc pair rows must fit 31 bits (score in chunks)");
+    return FBN_ERR_ARG;
+  }
+  RecFieldArgs a;
+  a.item_id = item_id; a.likes = likes; a.views = views; a.cache = cache; a.hist = hist; a.cate = cate;
+  a.table = table; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.Vc = Vc; a.Vc16 = Vc16; a.c = c; a.a_out = a_out;
+  a.err = err; a.V = V; a.U = U; a.m0 = m0; a.Mc = Mc; a.ldc = ldc; a.R = R; a.n_cate = n_cate; a.c16 = c_bf16;
+  const dim3 grid(rec_grid((long long)U * Mc, D)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  switch (D) {
+    case 16: fbn_launch(rec_fields_kernel<16>, grid, block, 0, st, a); break;
+    case 32: fbn_launch(rec_fields_kernel<32>, grid, block, 0, st, a); break;
+    case 64: fbn_launch(rec_fields_kernel<64>, grid, block, 0, st, a); break;
+    case 128: fbn_launch(rec_fields_kernel<128>, grid, block, 0, st, a); break;
+    default: fbn_launch(rec_fields_kernel<256>, grid, block, 0, st, a); break;
+  }
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}
+
+// ------------------------------------------------------------------------------ top-K selection
+// key = {ordered image of the f32 logit (32) | 0xFFFFFFFF - catalogue position (32)}: unique per
+// candidate, and a larger key is a larger logit or, on equal logits, a smaller position.  0 is the
+// "no candidate" key (excluded, filtered out, or an empty slot); a NaN logit takes the high word 1,
+// below -inf's 0x007FFFFF.
+#define REC_TILE 256     // keys a workgroup takes in per round
+#define REC_SEG 1024     // candidates per workgroup of the selection launch
+#define REC_KMAX 256
+
+struct RecTopkArgs {
+  const float* logits;        // mode 0: [U][Mc] chunk logits
+  const int64_t* item_id;     // [M] catalogue ids
+  const int64_t* item_seq;    // [U][L] or null
+  unsigned long long* carry;  // [U][K] running K best (mode 1: read, then rewritten)
+  unsigned long long* ws;     // [U][nseg][K] per-segment K best (mode 0: written; mode 1: read)
+  int64_t* out_index; int64_t* out_item; float* out_logit; float* out_prob;   // [U][K] (mode 1, optional)
+  unsigned* status;
+  int U, m0, Mc, L, exclude, K, nseg, mode;
+};
+
+__device__ __forceinline__ unsigned long long rec_key(float x, unsigned pos, bool& nan) {
+  const unsigned b = __float_as_uint(x);
+  nan = (b & 0x7FFFFFFFu) > 0x7F800000u;
+  const unsigned o = nan ? 1u : ((b & 0x80000000u) ? ~b : (b | 0x80000000u));
+  return ((unsigned long long)o << 32) | (unsigned long long)(0xFFFFFFFFu - pos);
+}
+__device__ __forceinline__ float rec_key_logit(unsigned long long key) {
+  const unsigned o = (unsigned)(key >> 32);
+  if (o == 1u) return __uint_as_float(0x7FC00000u);
+  return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
+}
+
+// One workgroup keeps the K largest of a key stream: buf[0, 256) is the running list (descending,
+// zeros past the keys seen), buf[256, 512) takes a tile of 256 new keys -- those that cannot enter
+// the K best (<= the current K-th) are dropped first, a tile left empty is skipped -- and a bitonic
+// sort of the 512 puts the K best back in front.
+// mode 0: the stream is segment blockIdx.x of user blockIdx.y's chunk logits -> ws[u][seg][K];
+// mode 1: the stream is the user's carried list followed by its segment lists -> carry[u][K] + outputs.
+__global__ void __launch_bounds__(256) rec_topk_kernel(RecTopkArgs p) {
+  __shared__ unsigned long long buf[2 * REC_TILE];
+  __shared__ long long hist[FBN_MAX_L];
+  const int t = threadIdx.x, u = blockIdx.y, seg = blockIdx.x;
+  const int K = p.K, L = p.item_seq ? p.L : 0;
+  buf[t] = 0ull;
+  int n, base = 0;
+  if (p.mode == 0) {
+    base = seg * REC_SEG;
+    n = min(REC_SEG, p.Mc - base);
+    if (t < L) hist[t] = p.item_seq[(size_t)u * L + t];
+  } else {
+    n = K * (1 + p.nseg);
+  }
+  __syncthreads();
+  for (int i0 = 0; i0 < n; i0 += REC_TILE) {
+    const int i = i0 + t;
+    unsigned long long key = 0ull;
+    if (i < n) {
+      if (p.mode == 0) {
+        const int j = base + i;
+        const long long m = (long long)p.m0 + j;
+        bool nan;
+        key = rec_key(p.logits[(size_t)u * p.Mc + j], (unsigned)m, nan);
+        if (nan) atomicOr(p.status, 1u);
+        if (p.exclude) {
+          const long long id = p.item_id[m];
+          bool ex = id == 0;
+          for (int l = 0; l < L; ++l) ex |= hist[l] != 0 && hist[l] == id;
+          if (ex) key = 0ull;
+        }
+      } else {
+        key = i < K ? p.carry[(size_t)u * K + i] : p.ws[(size_t)u * p.nseg * K + (i - K)];
+      }
+    }
+    if (key <= buf[K - 1]) key = 0ull;               // cannot enter the K best
+    if (!__syncthreads_or(key != 0ull)) continue;    // (workgroup-uniform)
+    buf[REC_TILE + t] = key;
+    __syncthreads();
+    for (int k = 2; k <= 2 * REC_TILE; k <<= 1) {
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+        const unsigned long long x = buf[lo], y = buf[hi];
+        const bool desc = (lo & k) == 0;
+        if ((x < y) == desc) { buf[lo] = y; buf[hi] = x; }
+        __syncthreads();
+      }
+    }
+  }
+  if (t >= K) return;
+  const unsigned long long key = buf[t];
+  if (p.mode == 0) {
+    p.ws[((size_t)u * p.nseg + seg) * K + t] = key;
+    return;
+  }
+  const size_t o = (size_t)u * K + t;
+  p.carry[o] = key;
+  if (!p.out_index) return;
+  if (key == 0ull) {
+    p.out_index[o] = -1;
+    p.out_item[o] = -1;
+    p.out_logit[o] = -__builtin_inff();
+    p.out_prob[o] = 0.f;
+  } else {
+    const unsigned pos = 0xFFFFFFFFu - (unsigned)key;
+    const float x = rec_key_logit(key);
+    p.out_index[o] = (int64_t)pos;
+    p.out_item[o] = p.item_id[pos];
+    p.out_logit[o] = x;
+    p.out_prob[o] = 1.f / (1.f + expf(-x));          // the head's sigmoid (mlp.hip head_lane)
+  }
+}
+
+static int rec_topk_check(int U, int Mc, int K) {
+  if (K < 1 || K > REC_KMAX) {
+    fbn_set_error("fbn_rec_topk: K must be in 1..256");
+    return FBN_ERR_ARG;
+  }
+  if (U < 0 || Mc < 0) {
+    fbn_set_error("fbn_rec_topk: negative U or Mc");
+    return FBN_ERR_ARG;
+  }
+  return FBN_OK;
+}
+
+extern "C" size_t fbn_rec_topk_workspace_size(int U, int Mc, int K) {
+  if (rec_topk_check(U, Mc, K)) return 0;
+  return (size_t)U * (size_t)fbn_cdiv(Mc, REC_SEG) * (size_t)K * sizeof(unsigned long long);
+}
+
+extern "C" int fbn_rec_topk(const float* logits, int U, int m0, int Mc, const int64_t* item_id,
+                            const int64_t* item_seq, int L, int exclude, int K, unsigned long long* carry, void* ws,
+                            size_t ws_bytes, int64_t* out_index, int64_t* out_item, float* out_logit, float* out_prob,
+                            unsigned* status, void* stream) {
+  if (int rc = rec_topk_check(U, Mc, K)) return rc;
+  if (L < 0 || L > FBN_MAX_L) {
+    fbn_set_error("fbn_rec_topk: history length L must be in 0..32");
+    return FBN_ERR_ARG;
+  }
+  if (m0 < 0 || (long long)U * Mc > 0x7FFFFFFFll || U > 65535) {
+    fbn_set_error("fbn_rec_topk: need m0 >= 0, U <= 65535 and U * Mc within 31 bits");
+    return FBN_ERR_ARG;
+  }
+  if (out_index && !(out_item && out_logit && out_prob)) {
+    fbn_set_error("fbn_rec_topk: the four outputs come together");
+    return FBN_ERR_ARG;
+  }
+  if (ws_bytes < fbn_rec_topk_workspace_size(U, Mc, K)) {
+    fbn_set_error("fbn_rec_topk: workspace smaller than fbn_rec_topk_workspace_size(U, Mc, K)");
+    return FBN_ERR_ARG;
+  }
+  if (U == 0) return FBN_OK;
+  RecTopkArgs a;
+  a.logits = logits; a.item_id = item_id; a.item_seq = L > 0 ? item_seq : nullptr; a.carry = carry;
+  a.ws = (unsigned long long*)ws; a.out_index = out_index; a.out_item = out_item; a.out_logit = out_logit;
+  a.out_prob = out_prob; a.status = status; a.U = U; a.m0 = m0; a.Mc = Mc; a.L = L; a.exclude = exclude; a.K = K;
+  a.nseg = fbn_cdiv(Mc, REC_SEG);
+  hipStream_t st = (hipStream_t)stream;
+  if (a.nseg > 0) {
+    a.mode = 0;
+    fbn_launch(rec_topk_kernel, dim3(a.nseg, U), dim3(256), 0, st, a);
+    FBN_CHECK_LAUNCH();
+  }
+  a.mode = 1;
+  fbn_launch(rec_topk_kernel, dim3(1, U), dim3(256), 0, st, a);
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}

@@ -18,7 +18,7 @@ import os
 
 import ctypes
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Callable, Dict, Optional
 
 import torch
 
@@ -360,6 +360,18 @@ class Collective:
 NO_COLLECTIVE = Collective()
 
 
+@dataclass
+class FieldsStage:
+    """A substitute for forward()'s field stage (the mm_proj GEMM + fbn_fields_fwd): `rows` rows whose
+    fields after SENET are produced elsewhere (recommend.py: composed from per-user and per-candidate
+    caches).  fill(Vc, Vc16, c, ldc, c_bf16, a_out, err, stream) writes the operands fbn_fields_fwd
+    would have written (a None pointer: not wanted in this mode); the bilinear, MLP and head launches
+    that follow are forward()'s own.  Inference only: no backward state (X, cnt, hmm) exists."""
+    rows: int
+    device: torch.device
+    fill: Callable
+
+
 def bn_train_stats(h, B, C, mean, invstd, run_mean, run_var, ntot, coll: Collective, stream, tiles=None):
     """Training-mode BatchNorm statistics over the GLOBAL batch (SyncBN when coll.world > 1).
     tiles: per-64-row-tile (sum, M2) partials written by the producing GEMM (no pass over h)."""
@@ -451,18 +463,27 @@ def forward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], cfg: Fwd
             masks_out: Optional[Dict[str, torch.Tensor]] = None, acts: Optional[Dict[str, torch.Tensor]] = None,
             probe: Optional[Dict[str, list]] = None, masks_in: Optional[Dict[str, torch.Tensor]] = None,
             after_gather=None, count_batches: bool = True, w16_ready: bool = False,
-            hooks: Optional[Dict[str, object]] = None) -> Dict[str, torch.Tensor]:
+            hooks: Optional[Dict[str, object]] = None,
+            fields: Optional[FieldsStage] = None) -> Dict[str, torch.Tensor]:
     """Run the forward; returns the activation dict (probs, logits and what backward needs).
 
     p: parameter tensors keyed like the reference state_dict (fp32, contiguous, on device).
     table_rows/pos: multi-GPU mode (rows already exchanged); otherwise p['item_emb.weight'] is read.
     sparse: {'map','slot_row'} to register touched rows for the native sparse-grad Adam.
     labels: if given, fuses BCE: acts['loss_terms'] and acts['gout'] (= dL/dlogit).
+    fields: a FieldsStage that replaces the field stage (batch is not read; eval mode only); every
+    launch from the bilinear on is the one this function issues for a batch of fields.rows rows.
     """
     d, L = cfg.d, cfg.L
-    item_id = batch["item_id"]
-    B = item_id.shape[0]
-    dev = item_id.device
+    if fields is not None:
+        if cfg.training or cfg.bilinear_each:
+            raise ValueError("forward(fields=...): eval mode and the 'all' bilinear only")
+        batch = {}
+        B, dev = fields.rows, fields.device
+    else:
+        item_id = batch["item_id"]
+        B = item_id.shape[0]
+        dev = item_id.device
     st = _lib.stream_handle(dev)
     ntot = B if ntot is None else ntot
     f32 = dict(dtype=torch.float32, device=dev)
@@ -477,7 +498,7 @@ def forward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], cfg: Fwd
 
     seq = batch.get("item_seq", None)
     Lr = 0 if seq is None else L
-    x_mm = batch["item_emb_d128"]
+    x_mm = batch["item_emb_d128"] if fields is None else None
     bf = cfg.bf16
     f16 = cfg.fwd16 and not bf            # bf16 forward GEMM operands only
     g16 = bf or f16                       # the forward GEMMs take bf16 operands
@@ -487,14 +508,15 @@ def forward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], cfg: Fwd
     a["s3w"] = s3w and (not w16_ready or bool(a.get("w16_images")))   # (the trainer's images carry lo too)
     w16 = (a["w16"] if w16_ready else bf16_weights(p, d, a, st, x=x_mm, images=s3w)) if g16 else None
     a["w16"] = w16
-    hmm = buf("hmm", (B, d))
-    gemm(w16["x"] if g16 else x_mm, w16["Wp"] if g16 else p["mm_proj.0.weight"], hmm, B, d, 128, 128, 128, d, False,
-         True, bias=p["mm_proj.0.bias"], bf16=g16, stream=st)
+    if fields is None:
+        hmm = buf("hmm", (B, d))
+        gemm(w16["x"] if g16 else x_mm, w16["Wp"] if g16 else p["mm_proj.0.weight"], hmm, B, d, 128, 128, 128, d,
+             False, True, bias=p["mm_proj.0.bias"], bf16=g16, stream=st)
     if hooks and "after_mmproj" in hooks:         # trainer: side-stream work forked here
         hooks["after_mmproj"]()
     if hooks and "before_gather" in hooks:        # trainer: the table rows' claims ran on the side stream
         hooks["before_gather"]()
-    X = buf("X", (B, 2, d))                     # fields 3 and 5 (the backward recomputes 1, 2, 4)
+    X = buf("X", (B, 2, d)) if fields is None else None   # fields 3 and 5 (the backward recomputes 1, 2, 4)
     # bf16 mode: the fields after SENET exist only as bf16 (GEMM operand and pair-kernel input)
     v16 = bf and not cfg.bilinear_each
     Vc = None if v16 else buf("Vc", (B, 5, d))
@@ -520,7 +542,7 @@ def forward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], cfg: Fwd
         a["s3_vc"] = buf("s3_vc_fwd", (2, 5 * B, d), torch.bfloat16)
         Vc16 = a["s3_vc"][0].view(B, 5, d)
     av = buf("a", (B, 6))
-    cnt = buf("cnt", (B,))
+    cnt = buf("cnt", (B,)) if fields is None else None
     if err is None:
         err = buf("err", (1,), torch.int32)
         err.zero_()
@@ -528,7 +550,9 @@ def forward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], cfg: Fwd
     V = p["item_emb.weight"].shape[0] if table_rows is None else 0
     sm = sparse or {}
     ev = _probe_start(probe, "fields_fwd")      # bench: the gather kernel's span
-    if _GATHER_HOT and table_rows is None and V * d * 4 < 0xFFFFFF00:
+    if fields is not None:
+        fields.fill(Vc, Vc16, None if split_c else c, KCp, int(bf), av, err, st)
+    elif _GATHER_HOT and table_rows is None and V * d * 4 < 0xFFFFFF00:
         # A/B variant: the batch's rows drawn >= _GATHER_HOT times are staged in LDS per workgroup
         hc = a.get("hot_cnt")
         if hc is None or hc.numel() != V:

@@ -1,0 +1,234 @@
+"""Top-K recommendation on the device: score a catalogue of M items for U users, keep the K best.
+
+The per-row paths (``FiBiNETTrainer.predict``, the drop-in module, ``predict.py``) score rows that
+each carry their own candidate and history.  Scoring every (user, candidate) pair through them
+re-gathers the history for every pair and re-runs the mm projection for every pair.  Here the pair's
+fields are composed from two caches (csrc/recommend.hip):
+
+* per candidate, once per catalogue: field 4 = ReLU(LN(mm_proj(item_emb_d128)))  (``refresh``)
+* per user, once per call:           field 5 = masked mean of the history rows
+
+and the rest of the forward (SENET, bilinear, MLP, head) is ``ops.forward``'s own launches on the pair
+rows, chunk by chunk, so a score is what the eval forward gives for that pair.  ``topk`` feeds every
+chunk's logits to ``fbn_rec_topk``, which carries each user's K best as integer keys: no score ever
+reaches the host and the U x M matrix is never sorted.
+
+Single device, bilinear "all"; a row-sharded table is out of scope.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import torch
+
+from . import _lib, ops
+from ._lib import call, ptr
+
+K_MAX = 256          # include/fibinet.h: fbn_rec_topk
+L_MAX = 32
+DEFAULT_CHUNK_ROWS = 131072
+CATALOGUE_KEYS = ("item_id", "likes_level", "views_level", "item_emb_d128")
+
+
+def _state_of(state) -> Dict[str, torch.Tensor]:
+    if isinstance(state, dict):
+        return state
+    if hasattr(state, "state_dict"):
+        if getattr(state, "world", 1) > 1:          # FiBiNETTrainer with a row-sharded table
+            raise ValueError("Recommender serves one device: pass the assembled state_dict of a world > 1 trainer")
+        return state.state_dict()
+    raise TypeError(f"state must be a state_dict, a FiBiNETTrainer or the model module, not {type(state).__name__}")
+
+
+class Recommender:
+    """Scores ``catalogue`` (a dict of ``item_id [M]``, ``likes_level [M]``, ``views_level [M]``,
+    ``item_emb_d128 [M, 128]``) for user histories with the weights of ``state`` (an App. B
+    ``state_dict``, a single-device ``FiBiNETTrainer`` or the drop-in module).  The compute dtype
+    follows ``model_cfg`` exactly as ``build_model`` reads it.  At most ``chunk_rows`` (user, candidate)
+    rows are live at a time.  Ids outside their tables never fault: they set a device flag that
+    ``check_ids()`` turns into the reference's ``IndexError``."""
+
+    def __init__(self, state, model_cfg: Dict, catalogue: Dict[str, torch.Tensor], *, device=None,
+                 max_len: int = 20, chunk_rows: Optional[int] = None):
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.type != "cuda":
+            raise RuntimeError(f"Recommender runs only on a HIP device, not {self.device} (no CPU fallback)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if not 0 <= int(max_len) <= L_MAX:
+            raise ValueError(f"max_len must be in 0..{L_MAX}")
+        self.max_len = int(max_len)
+        self.chunk_rows = int(chunk_rows) if chunk_rows is not None else DEFAULT_CHUNK_ROWS
+        if self.chunk_rows < 1:
+            raise ValueError("chunk_rows must be positive")
+        honour = bool(model_cfg.get("honour_config", False))
+        btype = model_cfg.get("bilinear_type", "all") if honour else "all"
+        if btype not in ("all", "each"):
+            raise ValueError("bilinear_type must be 'all' or 'each'")
+        if btype == "each":
+            raise NotImplementedError("Recommender supports bilinear_type 'all' only ('each' keeps one W per field: "
+                                      "score those models with FiBiNETTrainer.predict on expanded rows)")
+        cdt = str(model_cfg.get("compute_dtype", "fp32")).lower()
+        if cdt not in ("fp32", "float32", "bf16", "bfloat16", "bf16_fwd"):
+            raise ValueError(f"compute_dtype must be 'fp32', 'bf16' or 'bf16_fwd', not {cdt!r}")
+        self.d = int(model_cfg.get("embedding_dim", 64))
+        self._bf16 = cdt in ("bf16", "bfloat16")
+        self._fwd16 = cdt == "bf16_fwd"
+        missing = [k for k in CATALOGUE_KEYS if k not in catalogue]
+        if missing:
+            raise KeyError(f"catalogue lacks {missing}")
+        dev = self.device
+        self.cat = {k: catalogue[k].to(dev).long().contiguous() for k in CATALOGUE_KEYS[:3]}
+        self._x = catalogue["item_emb_d128"].to(dev).float().contiguous()
+        self.M = int(self.cat["item_id"].shape[0])
+        if self.M < 1 or any(int(t.shape[0]) != self.M for t in self.cat.values()) or \
+                tuple(self._x.shape) != (self.M, 128):
+            raise ValueError("catalogue columns must be [M] and item_emb_d128 [M, 128] with M >= 1")
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        # bit 0: a NaN logit reached the selection (it ranks below every number)
+        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._acts: Dict[int, Dict] = {}
+        self._probe: Optional[Dict[str, list]] = None      # tools/recommend_bench.py: ops.forward's kernel probes
+        self.refresh(state)
+
+    # ------------------------------------------------------------------ weights + item cache
+    @torch.no_grad()
+    def refresh(self, state) -> None:
+        """Take new weights and rebuild the item-side cache (field 4 of every catalogue row)."""
+        sd = _state_of(state)
+        dev, d = self.device, self.d
+        if "bilinear.W" not in sd:
+            raise NotImplementedError("Recommender supports bilinear_type 'all' only (state has no bilinear.W)")
+        if tuple(sd["item_emb.weight"].shape[1:]) != (d,):
+            raise ValueError(f"state has embedding_dim {sd['item_emb.weight'].shape[1]}, model_cfg says {d}")
+        p = {}
+        for k, v in sd.items():
+            t = v.detach().to(dev, copy=True)      # never aliases a live module's parameters
+            p[k] = (t.float() if t.is_floating_point() else t).contiguous()
+        self.p = p
+        self.V = int(p["item_emb.weight"].shape[0])
+        self.cfg = ops.FwdConfig(d=d, L=0, training=False, p_drop=0.0, bf16=self._bf16, fwd16=self._fwd16,
+                                 bilinear_each=False, R=int(p["senet.excitation.0.weight"].shape[0]))
+        g16 = self._bf16 or self._fwd16
+        with torch.cuda.device(dev):
+            st = _lib.stream_handle(dev)
+            self.err.zero_()
+            self._acts = {}
+            self._wimg: Dict = {}
+            self._w16 = None
+            hmm = torch.empty((self.M, d), dtype=torch.float32, device=dev)
+            if g16:
+                # bf16 images of the GEMM weights, once; the catalogue's x image only for this GEMM
+                w = ops.bf16_weights(p, d, self._wimg, st, x=self._x)
+                ops.gemm(w["x"], w["Wp"], hmm, self.M, d, 128, 128, 128, d, False, True, bias=p["mm_proj.0.bias"],
+                         bf16=True, stream=st)
+                self._w16 = {k: v for k, v in w.items() if k != "x"}
+                self._wimg.pop("w16_x", None)
+            else:
+                ops.gemm(self._x, p["mm_proj.0.weight"], hmm, self.M, d, 128, 128, 128, d, False, True,
+                         bias=p["mm_proj.0.bias"], stream=st)
+            self.cache = torch.empty((self.M, d), dtype=torch.float32, device=dev)
+            call("fbn_rec_item_cache", ptr(self.cat["item_id"]), ptr(self.cat["likes_level"]),
+                 ptr(self.cat["views_level"]), ptr(hmm), ptr(p["mm_proj.1.weight"]), ptr(p["mm_proj.1.bias"]),
+                 ops.LN_EPS, int(p["cate_emb.weight"].shape[0]), self.V, ptr(self.cache), ptr(self.err), self.M, d, st)
+
+    def check_ids(self) -> None:
+        """Raise the reference's IndexError if any id seen since construction (or the last refresh)
+        lay outside its embedding table (one 4-byte read)."""
+        if int(self.err.item()) & 1:
+            raise IndexError("index out of range in self (item/likes/views id outside its embedding table)")
+
+    # ------------------------------------------------------------------ the chunk loop
+    def _hist(self, item_seq: Optional[torch.Tensor], st):
+        dev, d = self.device, self.d
+        if item_seq is None:
+            seq, U, L = None, 1, 0
+        else:
+            if item_seq.dim() != 2:
+                raise ValueError("item_seq must be [U, L]")
+            seq = item_seq.to(dev).long()
+            if seq.shape[1] > self.max_len:
+                seq = seq[:, seq.shape[1] - self.max_len:]      # the collator keeps the last max_len
+            seq = seq.contiguous()
+            U, L = int(seq.shape[0]), int(seq.shape[1])
+            if U < 1:
+                raise ValueError("item_seq holds no user")
+        hist = torch.empty((U, d), dtype=torch.float32, device=dev)
+        call("fbn_rec_hist_pool", ptr(seq) if L else None, ptr(self.p["item_emb.weight"]), self.V, ptr(hist),
+             ptr(self.err), U, L, d, st)
+        return seq if L else None, hist, U, L
+
+    def _chunks(self, U: int):
+        mc = max(1, self.chunk_rows // U)
+        for m0 in range(0, self.M, mc):
+            yield m0, min(mc, self.M - m0)
+
+    def _forward_chunk(self, hist, U, m0, Mc) -> Dict:
+        """The eval forward's activations of one chunk: a["logits"] / a["probs"] [U * Mc], row u * Mc + j
+        = user u, candidate m0 + j; the buffers are reused by the next chunk of the same size."""
+        p, c, dev = self.p, self.cat, self.device
+
+        def fill(Vc, Vc16, cbuf, ldc, c_bf16, a_out, err, st):
+            call("fbn_rec_fields", ptr(c["item_id"]), ptr(c["likes_level"]), ptr(c["views_level"]), ptr(self.cache),
+                 ptr(hist), ptr(p["cate_emb.weight"]), int(p["cate_emb.weight"].shape[0]),
+                 ptr(p["item_emb.weight"]), self.V, ptr(p["senet.excitation.0.weight"]),
+                 ptr(p["senet.excitation.0.bias"]), ptr(p["senet.excitation.2.weight"]),
+                 ptr(p["senet.excitation.2.bias"]), self.cfg.R, ptr(Vc), ptr(Vc16), ptr(cbuf), ldc, c_bf16,
+                 ptr(a_out), ptr(err), U, m0, Mc, self.d, st)
+
+        rows = U * Mc
+        acts = self._acts.get(rows)
+        if acts is None:
+            if len(self._acts) >= 4:                 # a few shapes recur (full and ragged chunk)
+                self._acts.clear()
+            acts = self._acts[rows] = {}
+        if self._w16 is not None:
+            acts["w16"] = self._w16
+        a = ops.forward(p, None, self.cfg, None, err=self.err, acts=acts, w16_ready=self._w16 is not None,
+                        fields=ops.FieldsStage(rows, dev, fill), probe=self._probe)
+        return a
+
+    # ------------------------------------------------------------------ public
+    @torch.no_grad()
+    def score(self, item_seq: Optional[torch.Tensor], logits: bool = False) -> torch.Tensor:
+        """Probabilities (or logits) [U, M] of every (user, catalogue item) pair; ``item_seq=None``:
+        one cold user whose history field is zero."""
+        with torch.cuda.device(self.device):
+            st = _lib.stream_handle(self.device)
+            _, hist, U, _ = self._hist(item_seq, st)
+            out = torch.empty((U, self.M), dtype=torch.float32, device=self.device)
+            for m0, Mc in self._chunks(U):
+                a = self._forward_chunk(hist, U, m0, Mc)
+                out[:, m0:m0 + Mc].copy_((a["logits"] if logits else a["probs"]).view(U, Mc))
+        return out
+
+    @torch.no_grad()
+    def topk(self, item_seq: Optional[torch.Tensor], k: int, exclude_history: bool = True) -> Dict[str, torch.Tensor]:
+        """Each user's k best catalogue items, best first: ``index`` (catalogue position, int64),
+        ``item_id``, ``logit``, ``prob``, all [U, k].  Ranked on logits; equal logits go to the smaller
+        position.  exclude_history: items of the user's own history and padding items (id 0) are never
+        returned.  With fewer than k eligible items the tail is index -1, item_id -1, logit -inf, prob 0.
+        Nothing is copied to the host and nothing synchronises."""
+        k = int(k)
+        if not 1 <= k <= K_MAX:
+            raise ValueError(f"k must be in 1..{K_MAX}")
+        dev = self.device
+        with torch.cuda.device(dev):
+            st = _lib.stream_handle(dev)
+            seq, hist, U, L = self._hist(item_seq, st)
+            carry = torch.zeros((U, k), dtype=torch.int64, device=dev)
+            out = {"index": torch.empty((U, k), dtype=torch.int64, device=dev),
+                   "item_id": torch.empty((U, k), dtype=torch.int64, device=dev),
+                   "logit": torch.empty((U, k), dtype=torch.float32, device=dev),
+                   "prob": torch.empty((U, k), dtype=torch.float32, device=dev)}
+            chunks = list(self._chunks(U))
+            nws = int(_lib.lib().fbn_rec_topk_workspace_size(U, chunks[0][1], k))
+            ws = torch.empty(max(1, (nws + 7) // 8), dtype=torch.int64, device=dev)
+            for i, (m0, Mc) in enumerate(chunks):
+                a = self._forward_chunk(hist, U, m0, Mc)
+                last = i == len(chunks) - 1
+                call("fbn_rec_topk", ptr(a["logits"]), U, m0, Mc, ptr(self.cat["item_id"]), ptr(seq), L,
+                     int(bool(exclude_history)), k, ptr(carry), ptr(ws), nws,
+                     ptr(out["index"]) if last else None, ptr(out["item_id"]) if last else None,
+                     ptr(out["logit"]) if last else None, ptr(out["prob"]) if last else None, ptr(self.status), st)
+        return out

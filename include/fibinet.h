@@ -647,6 +647,52 @@ size_t fbn_eval_workspace_size(long long n);
 int fbn_eval_reduce(const uint32_t* keys, long long n, void* ws, size_t ws_bytes, void* out, unsigned* status,
                     void* stream);
 
+/* ---------------------------------------------------------------- serving: catalogue scoring + top-K
+ * Replaces the per-row scoring loop of src/Prediction.py:106-113 when the rows are the U x M pairs
+ * (user u, catalogue item m): the field construction of src/model_fibinet.py:152-188 is split into
+ * what depends on the candidate only, on the user only, and on the pair.  The tail of the forward
+ * (bilinear, MLP, head) runs unchanged on the pair rows.  D in {16,32,64,128,256}; L <= 32; id range
+ * violations set bit 0 of the sticky *err as fbn_fields_fwd does.
+ *
+ * fbn_rec_item_cache: cache[m] = ReLU(LayerNorm(hmm[m])) (f32 [M][D]) from the pre-LN projection hmm
+ * [M][D] of the catalogue's item_emb_d128 -- the mm_proj LayerNorm + ReLU of src/model_fibinet.py:107-108,
+ * 162, once per catalogue instead of once per pair; validates item_id / likes / views [M]. */
+int fbn_rec_item_cache(const int64_t* item_id, const int64_t* likes, const int64_t* views, const float* hmm,
+                       const float* ln_g, const float* ln_b, float ln_eps, int n_cate, long long V, float* cache,
+                       int* err, int M, int D, void* stream);
+/* fbn_rec_hist_pool: hist[u] = sum_{t: s_t != 0} E[s_t] / max(1, #nonzero) (f32 [U][D]) of the histories
+ * item_seq [U][L] -- the masked history mean of src/model_fibinet.py:165-176, once per user instead of
+ * once per pair, summed in slot order like fbn_fields_fwd (same bits).  item_seq == NULL (or L = 0):
+ * zero rows, the reference's hist_feat = zeros branch. */
+int fbn_rec_hist_pool(const int64_t* item_seq, const float* table, long long V, float* hist, int* err, int U, int L,
+                      int D, void* stream);
+/* fbn_rec_fields: pair rows p = u * Mc + (m - m0) for the candidates [m0, m0 + Mc) and all U users:
+ * X1 = cate[likes[m]], X2 = cate[views[m]], X3 = table[item_id[m]], X4 = cache[m], X5 = hist[u], then
+ * SENetLayer.forward (src/model_fibinet.py:24-35, 180-188).  Outputs as fbn_fields_fwd's forward
+ * operands, each optional: Vc (f32) / Vc16 (bf16) [P][5][D], the V block of c [P][ldc] (f32, or bf16
+ * when c_bf16), a_out [P][6] -- the same device functions in the same order, so the same bits.
+ * U * Mc < 2^31. */
+int fbn_rec_fields(const int64_t* item_id, const int64_t* likes, const int64_t* views, const float* cache,
+                   const float* hist, const float* cate, int n_cate, const float* table, long long V, const float* w1,
+                   const float* b1, const float* w2, const float* b2, int R, float* Vc, short* Vc16, void* c, int ldc,
+                   int c_bf16, float* a_out, int* err, int U, int m0, int Mc, int D, void* stream);
+/* fbn_rec_topk: each user's K best of the chunk's logits [U][Mc] (candidates [m0, m0 + Mc)) merged into
+ * the carried list carry [U][K] (uint64 keys, zero before the first chunk), so chunks stream; replaces a
+ * host-side sort of the U x M scores.  key = {order-preserving image of the f32 logit, 0xFFFFFFFF -
+ * catalogue position}: keys are unique, a larger key is a larger logit or, on equal logits, the smaller
+ * position, so the result does not depend on the chunking.  A NaN logit ranks below every number and
+ * sets bit 0 of *status.  exclude != 0: a candidate whose item_id is 0 (padding) or equals a non-padding
+ * id of item_seq[u] ([U][L], may be NULL) is never returned.  Outputs (optional, together) [U][K]:
+ * catalogue position, its item_id, logit, sigmoid(logit), best first; with fewer than K eligible
+ * candidates the tail is position -1, item_id -1, logit -inf, probability 0.  1 <= K <= 256 (else
+ * FBN_ERR_ARG, checked on the host before any device work); ws >= fbn_rec_topk_workspace_size(U, Mc, K)
+ * bytes (host-only query; 0 for an invalid K).  Two launches: per (user, 1024-candidate segment) a
+ * bitonic selection in LDS, then per user the merge of its segments with the carry. */
+size_t fbn_rec_topk_workspace_size(int U, int Mc, int K);
+int fbn_rec_topk(const float* logits, int U, int m0, int Mc, const int64_t* item_id, const int64_t* item_seq, int L,
+                 int exclude, int K, unsigned long long* carry, void* ws, size_t ws_bytes, int64_t* out_index,
+                 int64_t* out_item, float* out_logit, float* out_prob, unsigned* status, void* stream);
+
 /* ---------------------------------------------------------------- step programs (native step driver)
  * Replaces the Python loop body that issues one training step (src/train_fibinet.py:113-123): the
  * host records a step's calls of this library -- entry point, arguments, and the cross-stream

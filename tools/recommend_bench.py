@@ -1,0 +1,156 @@
+"""Top-K recommendation: the serving path vs expanded rows, timed in one process (not part of bench.py).
+
+C3-shaped weights (d = 128, bf16, the reference's 91,718-row table as the catalogue), U = 64 user
+histories of L = 20, K = 10:
+  (a) topk_ms       Recommender.topk: per-user and per-candidate caches, pair composition, the eval
+                    forward's tail per chunk, device-side selection
+  (b) expanded_ms   the route without it: the U x M pairs expanded into ordinary batches of 8192 rows
+                    (row gathers on the device), each through the eval forward (ops.forward, same
+                    weights and dtype), the logits collected into [U, M], then torch.topk
+Each figure is the median of RUNS timed runs after a warm-up (HIP events, one process, the two routes
+interleaved).  stage_ms: kernel spans of (a)'s stages summed over the chunks of one probed run (the
+library's kernel probes; "forward" is the whole chunk forward, fields included).
+
+    python tools/recommend_bench.py [--users 64] [--out profiles/recommend_vs_expanded.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from ctr_recommendation_amd import _lib, ops
+from ctr_recommendation_amd.model_fibinet import build_model
+from ctr_recommendation_amd.recommend import Recommender
+
+RUNS = 10
+
+
+def _span(probes):
+    return sum(max(0.0, kp.elapsed_time()) for kp, _ in probes)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--users", type=int, default=64)
+    ap.add_argument("--items", type=int, default=91718)
+    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--d", type=int, default=128)
+    ap.add_argument("--dtype", default="bf16")
+    ap.add_argument("--batch", type=int, default=8192)
+    ap.add_argument("--chunk-rows", type=int, default=None)
+    ap.add_argument("--runs", type=int, default=RUNS)
+    ap.add_argument("--out", default=os.path.join("profiles", "recommend_vs_expanded.json"))
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    U, M, K, d, L, B = args.users, args.items, args.k, args.d, 20, args.batch
+    cfg = {"embedding_dim": d, "vocab_size": M, "compute_dtype": args.dtype}
+    torch.manual_seed(3)
+    model = build_model(None, cfg).eval()
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn((M, 128), generator=g)
+    cat = {"item_id": torch.arange(M), "likes_level": torch.randint(0, 11, (M,), generator=g),
+           "views_level": torch.randint(0, 11, (M,), generator=g), "item_emb_d128": x / x.norm(dim=1, keepdim=True)}
+    seq = torch.randint(1, M, (U, L), generator=g)
+    seq[torch.rand((U, L), generator=g) < 0.3] = 0
+    seq = seq.to(dev)
+    rec = Recommender(model.state_dict(), cfg, cat, device=dev, chunk_rows=args.chunk_rows)
+    catd = {k: v.to(dev) for k, v in rec.cat.items()}
+    catd["item_emb_d128"] = rec._x
+    fcfg = ops.FwdConfig(**{**rec.cfg.__dict__, "L": L})
+    acts = {}
+
+    def expanded():
+        out = torch.empty(U * M, dtype=torch.float32, device=dev)
+        for r0 in range(0, U * M, B):
+            r = torch.arange(r0, min(r0 + B, U * M), device=dev)
+            u, m = r // M, r % M
+            batch = {k: v[m] for k, v in catd.items()}
+            batch["item_seq"] = seq[u]
+            a = ops.forward(rec.p, batch, fcfg, acts=acts.setdefault(r.numel(), {}))
+            out[r0:r0 + r.numel()] = a["logits"]
+        return torch.topk(out.view(U, M), K, dim=1)
+
+    def serving():
+        return rec.topk(seq, K, exclude_history=False)
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        r = fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b), r
+
+    serving(), expanded()                                   # warm-up (allocations, bf16 images)
+    ta, tb = [], []
+    for _ in range(args.runs):                              # interleaved A/B
+        t, ra = timed(serving)
+        ta.append(t)
+        t, rb = timed(expanded)
+        tb.append(t)
+    rec.check_ids()
+    same = (ra["index"] == rb.indices).float().mean().item()
+
+    # one probed run of (a): kernel spans per stage, summed over the chunks
+    stages = {}
+    probe = {}
+    rec._probe = probe
+    call0 = _lib.call
+
+    def probed_call(name, *a):
+        if name in ("fbn_rec_hist_pool", "fbn_rec_topk"):
+            kp = _lib.KernelProbe()
+            stages.setdefault(name, []).append((kp, None))
+            try:
+                return call0(name, *a)
+            finally:
+                kp.done()
+        return call0(name, *a)
+
+    import ctr_recommendation_amd.recommend as rmod
+    rmod.call = probed_call
+    serving()
+    torch.cuda.synchronize()
+    rmod.call = call0
+    rec._probe = None
+    stage_ms = {"hist_pool": _span(stages["fbn_rec_hist_pool"]), "fields": _span(probe["fields_fwd"]),
+                "gemm_mlp0": _span(probe["gemm_mlp0"]), "topk": _span(stages["fbn_rec_topk"])}
+    whole = []
+    fwd0 = rec._forward_chunk
+
+    def probed_forward(*a):
+        kp = _lib.KernelProbe()
+        whole.append((kp, None))
+        try:
+            return fwd0(*a)
+        finally:
+            kp.done()
+
+    rec._forward_chunk = probed_forward
+    serving()
+    torch.cuda.synchronize()
+    rec._forward_chunk = fwd0
+    stage_ms["forward"] = _span(whole)
+
+    ma, mb = statistics.median(ta), statistics.median(tb)
+    out = {"device": torch.cuda.get_device_name(dev), "users": U, "items": M, "k": K, "d": d, "dtype": args.dtype,
+           "expanded_batch": B, "chunk_rows": rec.chunk_rows, "chunks": len(list(rec._chunks(U))), "runs": args.runs,
+           "statistic": "median", "topk_ms": round(ma, 3), "expanded_ms": round(mb, 3),
+           "ratio_expanded_over_topk": round(mb / ma, 3), "topk_ms_min_max": [round(min(ta), 3), round(max(ta), 3)],
+           "expanded_ms_min_max": [round(min(tb), 3), round(max(tb), 3)],
+           "stage_ms": {k: round(v, 3) for k, v in stage_ms.items()},
+           "index_agreement_with_expanded": round(same, 6)}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
