@@ -50,6 +50,7 @@ SIGNATURES = {
     "fbn_colsum_partial": (I, [P, I, I, I, P, P]),
     "fbn_sum_jobs": (I, [P, I, P]),
     "fbn_sum_jobs2": (I, [P, I, P, I, P]),
+    "fbn_sum_jobs_sq": (I, [P, I, P, I, P, I, P, P]),
     "fbn_gemm_slabs_size": (SZ, [I, I, I]),
     "fbn_gemm_slabs": (I, [P, P, I, I, I, I, I, I, I, P, SZ, P, I, I, P, I, I, P, P]),
     "fbn_gemm_slabs_split": (I, [I, I, I]),
@@ -66,6 +67,8 @@ SIGNATURES = {
                            I, I, P]),
     "fbn_fields_bwd_img": (I, [P, P, P, P, P, P, P, F, P, P, P, I, I, P, P, P, P, P, P, P, P, P, P, P, P, LL, P, P, I,
                                I, I, I, P]),
+    "fbn_fields_bwd_slot": (I, [P, P, P, P, P, P, P, F, P, P, P, I, I, P, P, P, P, P, P, P, I, P, P, P, I, LL, P, P, P,
+                                LL, I, I, I, P]),
     "fbn_pairs_fwd": (I, [P, P, P, P, I, I, I, I, I, P]),
     "fbn_pairs_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I, P]),
     "fbn_pairs_fwd_img": (I, [P, P, P, P, I, I, I, P]),

@@ -332,6 +332,9 @@ struct FieldBwdArgs {
   // per-sample vectors gvec[b][0] = dX3 (item row), gvec[b][1] = dX5/count (each history row)
   float* gtab; float* gvec;
   double* gnorm;       // optional with gvec: [B][2] sums of squares of the two vectors (clip norm)
+  // slot form (fbn_fields_bwd_slot): gvec is the base of the deferred-gradient ring [ring_n][ring_stride];
+  // the vectors go to slot *slot_step % ring_n and that slot's address to *slot_cell (FBN_GRAD_CELL readers)
+  const int* slot_step; float** slot_cell; long long ring_stride; int ring_n;
   // mode 1: rows written to sendbuf at pos[b][t] (f32); mode 2: the same in bf16 (bf16 mode's wire)
   const int* pos; void* sendbuf;
   long long V;
@@ -370,7 +373,7 @@ __device__ __forceinline__ void atomic_add_row_t(float* row, const f32x4& t, int
 // read-modify-write into a per-wave LDS slice with the wave's sample groups taking turns; each
 // wave folds its groups with shuffles into its slice, and the block sums its 4 slices into its
 // partial row (same layout as before).
-template <int D, int MODE, int RMAX>
+template <int D, int MODE, int RMAX, bool SLOT = false>
 __global__ void __launch_bounds__(256) fields_bwd_kernel(FieldBwdArgs p) {
   FBN_MAIN_PRIO();
   constexpr int G = D / 4;
@@ -396,6 +399,11 @@ __global__ void __launch_bounds__(256) fields_bwd_kernel(FieldBwdArgs p) {
   const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int nwaves = (gridDim.x * blockDim.x) >> 6;
   const int L = p.L;
+  float* gvec = p.gvec;
+  if constexpr (SLOT) {   // the ring slot of this step, chosen on the device (as fbn_owner_fold); wave-uniform
+    gvec += (size_t)(__builtin_amdgcn_readfirstlane(*p.slot_step) % p.ring_n) * p.ring_stride;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *p.slot_cell = gvec;
+  }
   f32x4 acc_lg = {0.f, 0.f, 0.f, 0.f}, acc_lb = {0.f, 0.f, 0.f, 0.f}, acc_hb = {0.f, 0.f, 0.f, 0.f};
   float acc_se[SJ];
 #pragma unroll
@@ -527,8 +535,8 @@ __global__ void __launch_bounds__(256) fields_bwd_kernel(FieldBwdArgs p) {
       const f32x4 gh = dx[4] / p.cnt[b];
       if (MODE == 0 && p.gvec) {
         // sparse mode: plain stores; rows are resolved later through map / slot_row
-        *reinterpret_cast<f32x4*>(p.gvec + (size_t)b * 2 * D + 4 * q) = dx[2];
-        *reinterpret_cast<f32x4*>(p.gvec + ((size_t)b * 2 + 1) * D + 4 * q) = gh;
+        *reinterpret_cast<f32x4*>(gvec + (size_t)b * 2 * D + 4 * q) = dx[2];
+        *reinterpret_cast<f32x4*>(gvec + ((size_t)b * 2 + 1) * D + 4 * q) = gh;
         if (p.gnorm) {
           double si = 0.0, sh = 0.0;
 #pragma unroll
@@ -794,17 +802,17 @@ extern "C" int fbn_fields_bwd_partials_size(int D, int R, int n_cate) { return 1
 // rows of the `partials` scratch the caller allocates: one per block
 extern "C" int fbn_fields_bwd_grid(int B, int D) { return fields_grid(B, D, FBN_FB_MAXBLK); }
 
-template <int MODE, int RMAX>
+template <int MODE, int RMAX, bool SLOT = false>
 static int launch_fields_bwd_r(const FieldBwdArgs& a, int D, hipStream_t st) {
   const int grid = fields_grid(a.B, D, FBN_FB_MAXBLK);
   const size_t lds = (4 * (size_t)(13 * a.R + 6 + 3 * D + a.n_cate * D) + 4 * (64 / (D / 4)) * (12 + 2 * RMAX)) *
                      sizeof(float);   // 4 wave slices + SENET staging
   switch (D) {
-    case 16: fbn_launch((fields_bwd_kernel<16, MODE, RMAX>), dim3(grid), dim3(256), lds, st, a); break;
-    case 32: fbn_launch((fields_bwd_kernel<32, MODE, RMAX>), dim3(grid), dim3(256), lds, st, a); break;
-    case 64: fbn_launch((fields_bwd_kernel<64, MODE, RMAX>), dim3(grid), dim3(256), lds, st, a); break;
-    case 128: fbn_launch((fields_bwd_kernel<128, MODE, RMAX>), dim3(grid), dim3(256), lds, st, a); break;
-    case 256: fbn_launch((fields_bwd_kernel<256, MODE, RMAX>), dim3(grid), dim3(256), lds, st, a); break;
+    case 16: fbn_launch((fields_bwd_kernel<16, MODE, RMAX, SLOT>), dim3(grid), dim3(256), lds, st, a); break;
+    case 32: fbn_launch((fields_bwd_kernel<32, MODE, RMAX, SLOT>), dim3(grid), dim3(256), lds, st, a); break;
+    case 64: fbn_launch((fields_bwd_kernel<64, MODE, RMAX, SLOT>), dim3(grid), dim3(256), lds, st, a); break;
+    case 128: fbn_launch((fields_bwd_kernel<128, MODE, RMAX, SLOT>), dim3(grid), dim3(256), lds, st, a); break;
+    case 256: fbn_launch((fields_bwd_kernel<256, MODE, RMAX, SLOT>), dim3(grid), dim3(256), lds, st, a); break;
     default: fbn_set_error("fields: embedding_dim must be one of 16,32,64,128,256"); return FBN_ERR_UNSUPPORTED;
   }
   FBN_CHECK_LAUNCH();
@@ -814,6 +822,9 @@ static int launch_fields_bwd_r(const FieldBwdArgs& a, int D, hipStream_t st) {
 // the reference's SENET width is 3 (reduction ratio 3 over 6 fields): register arrays sized 3
 template <int MODE>
 static int launch_fields_bwd(const FieldBwdArgs& a, int D, hipStream_t st) {
+  if constexpr (MODE == 0)   // the slot form: an instantiation of its own, the other entry points' code unchanged
+    if (a.slot_step)
+      return a.R <= 3 ? launch_fields_bwd_r<0, 3, true>(a, D, st) : launch_fields_bwd_r<0, FBN_MAXR, true>(a, D, st);
   return a.R <= 3 ? launch_fields_bwd_r<MODE, 3>(a, D, st) : launch_fields_bwd_r<MODE, FBN_MAXR>(a, D, st);
 }
 
@@ -827,7 +838,8 @@ static int fields_bwd_impl(const int64_t* item_id, const int64_t* item_seq, cons
                            const float* cate, const float* X, const float* a, const float* cnt, const float* dV,
                            float* dhmm, short* dhmm16, float* partials, float* const* param_grads, float* gtab,
                            float* gvec, double* gnorm, long long V, const int* pos, void* sendbuf, int send_bf16,
-                           int B, int L, int D, void* stream, long long dhmm16_lo);
+                           int B, int L, int D, void* stream, long long dhmm16_lo, const int* slot_step = nullptr,
+                           void* slot_cell = nullptr, int ring_n = 0, long long ring_stride = 0);
 extern "C" int fbn_fields_bwd(const int64_t* item_id, const int64_t* item_seq, const int64_t* likes,
                               const int64_t* views, const float* hmm, const float* ln_g, const float* ln_b,
                               float ln_eps, const float* w1, const float* b1, const float* w2, int R, int n_cate,
@@ -852,13 +864,35 @@ extern "C" int fbn_fields_bwd_img(const int64_t* item_id, const int64_t* item_se
                          cnt, dV, dhmm, (short*)dhmm_img, partials, param_grads, gtab, gvec, gnorm, V, pos, sendbuf,
                          send_bf16, B, L, D, stream, (long long)B * D);
 }
+// The single-GPU trainer's form: the per-sample vectors written straight into deferred-gradient ring
+// slot *step % ring_n of ring [ring_n][ring_stride] (ring_stride >= B*2*D floats), the slot's address
+// to *cell -- the fold, the norm and the step tail read them there through Lp1 | FBN_GRAD_CELL, and the
+// tail has nothing to copy.  dhmm_is_img: dhmm16 holds split images (fbn_fields_bwd_img).
+extern "C" int fbn_fields_bwd_slot(const int64_t* item_id, const int64_t* item_seq, const int64_t* likes,
+                                   const int64_t* views, const float* hmm, const float* ln_g, const float* ln_b,
+                                   float ln_eps, const float* w1, const float* b1, const float* w2, int R, int n_cate,
+                                   const float* cate, const float* X, const float* a, const float* cnt, const float* dV,
+                                   float* dhmm, void* dhmm16, int dhmm_is_img, float* partials,
+                                   float* const* param_grads, float* ring, int ring_n, long long ring_stride,
+                                   const int* step, void* cell, double* gnorm, long long V, int B, int L, int D,
+                                   void* stream) {
+  if (!ring || !step || !cell || ring_n < 1 || ring_stride < (long long)B * 2 * D || (ring_stride & 3) ||
+      ((uintptr_t)ring & 15) || (dhmm_is_img && !dhmm16)) {
+    fbn_set_error("fbn_fields_bwd_slot: ring (16-B aligned), step, cell; ring_n >= 1, ring_stride >= B*2*D, % 4 == 0");
+    return FBN_ERR_ARG;
+  }
+  return fields_bwd_impl(item_id, item_seq, likes, views, hmm, ln_g, ln_b, ln_eps, w1, b1, w2, R, n_cate, cate, X, a,
+                         cnt, dV, dhmm, (short*)dhmm16, partials, param_grads, nullptr, ring, gnorm, V, nullptr, nullptr,
+                         0, B, L, D, stream, dhmm_is_img ? (long long)B * D : 0, step, cell, ring_n, ring_stride);
+}
 static int fields_bwd_impl(const int64_t* item_id, const int64_t* item_seq, const int64_t* likes,
                            const int64_t* views, const float* hmm, const float* ln_g, const float* ln_b,
                            float ln_eps, const float* w1, const float* b1, const float* w2, int R, int n_cate,
                            const float* cate, const float* X, const float* a, const float* cnt, const float* dV,
                            float* dhmm, short* dhmm16, float* partials, float* const* param_grads, float* gtab,
                            float* gvec, double* gnorm, long long V, const int* pos, void* sendbuf, int send_bf16,
-                           int B, int L, int D, void* stream, long long dhmm16_lo) {
+                           int B, int L, int D, void* stream, long long dhmm16_lo, const int* slot_step,
+                           void* slot_cell, int ring_n, long long ring_stride) {
   if (B <= 0) return FBN_OK;
   if (L < 0 || L > 32 || R < 1 || R > FBN_MAXR) { fbn_set_error("fbn_fields_bwd: bad L/R"); return FBN_ERR_ARG; }
   FieldBwdArgs p;
@@ -866,6 +900,7 @@ static int fields_bwd_impl(const int64_t* item_id, const int64_t* item_seq, cons
   p.hmm = hmm; p.ln_g = ln_g; p.ln_b = ln_b; p.w1 = w1; p.b1 = b1; p.w2 = w2; p.cate = cate;
   p.X = X; p.a = a; p.cnt = cnt; p.dV = dV; p.dhmm = dhmm; p.dhmm16 = dhmm16; p.partials = partials;
   p.dhmm16_lo = dhmm16_lo;
+  p.slot_step = slot_step; p.slot_cell = (float**)slot_cell; p.ring_n = ring_n; p.ring_stride = ring_stride;
   p.gtab = gtab; p.gvec = gvec; p.gnorm = gvec ? gnorm : nullptr; p.pos = pos; p.sendbuf = sendbuf;
   p.V = V; p.B = B; p.L = L; p.R = R; p.n_cate = n_cate; p.ln_eps = ln_eps;
   hipStream_t st = (hipStream_t)stream;

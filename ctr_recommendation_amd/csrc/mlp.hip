@@ -931,7 +931,7 @@ struct SumJob {
   int nch, C;
   float scale, beta;
   int ld;
-  int pad_;
+  int sq;   // fbn_sum_jobs_sq: 1 = the output is a dense gradient, its squares join the clip norm
 };
 struct SlabJob {
   const float* ws;
@@ -943,6 +943,13 @@ struct SlabJob {
 #define FBN_SUM_WIDE 32        // jobs with at least this many columns take 16 columns per block
 #define FBN_MAX_SLAB_JOBS 8
 #define FBN_SLAB_GROUPS 4      // slab groups per output quad (256 threads = 64 quads x 4 groups)
+#define FBN_SUMSQ_SLOTS 64     // the clip norm's accumulator slots (optim.hip, include/fibinet.h)
+#define FBN_MAX_SQ_RANGES 24   // fbn_sum_jobs_sq: (pointer, count) ranges squared by extra blocks
+#define FBN_SQ_RANGE_BLOCK 1024   // elements of a range per block
+struct SqRange {
+  const float* x;
+  long long n;
+};
 struct SumJobs {
   SumJob j[FBN_MAX_SUM_JOBS];
   int col0[FBN_MAX_SUM_JOBS + 1];
@@ -951,13 +958,25 @@ struct SumJobs {
   int blk0[FBN_MAX_SLAB_JOBS + 1];   // first block of each slab job (after the column blocks)
   int ns;
 };
+// fbn_sum_jobs_sq: the clip norm's dense part in the same launch -- every block adds the squares of the
+// outputs it has just written (sum jobs with sq = 1, every slab job) to the norm slots, and blocks past
+// the slab blocks square the ranges (gradients final before the launch)
+struct SumSq {
+  double* out;                        // [FBN_SUMSQ_SLOTS]
+  SqRange r[FBN_MAX_SQ_RANGES];
+  int rblk0[FBN_MAX_SQ_RANGES + 1];   // first block of each range (after the slab blocks)
+  int nr;
+};
+__device__ __forceinline__ double sq4(const f32x4& t) {
+  return ((double)(t[0] * t[0]) + (double)(t[1] * t[1])) + ((double)(t[2] * t[2]) + (double)(t[3] * t[3]));
+}
 // slab jobs of at most FBN_SLAB_DIRECT slabs: one output quad per thread, every slab's load in
 // flight at once, summed in slab order (no LDS fold; a quarter of the blocks)
 #define FBN_SLAB_DIRECT 8
-__device__ __forceinline__ void slab_direct(const SlabJob& sj, int lb) {
+__device__ __forceinline__ double slab_direct(const SlabJob& sj, int lb) {
   const size_t total = (size_t)sj.M * sj.N;
   const size_t i4 = (size_t)lb * 256 + threadIdx.x;
-  if (i4 >= total / 4) return;
+  if (i4 >= total / 4) return 0.0;
   const float* src = sj.ws + i4 * 4;
   f32x4 x[FBN_SLAB_DIRECT];
 #pragma unroll
@@ -971,16 +990,15 @@ __device__ __forceinline__ void slab_direct(const SlabJob& sj, int lb) {
   float* cp = sj.out + (size_t)m * sj.ldc + n + (n < sj.seg ? sj.off0 : sj.off1);
   if (sj.beta != 0.f) t += sj.beta * *reinterpret_cast<const f32x4*>(cp);
   *reinterpret_cast<f32x4*>(cp) = t;
+  return sq4(t);
 }
-__device__ __forceinline__ void slab_block(const SumJobs& J, int gb) {
+// (both return the squares of what this thread wrote, for fbn_sum_jobs_sq)
+__device__ __forceinline__ double slab_block(const SumJobs& J, int gb) {
   __shared__ f32x4 red[FBN_SLAB_GROUPS][64];
   int u = 0;
   while (u + 1 < J.ns && gb >= J.blk0[u + 1]) ++u;
   const SlabJob sj = J.s[u];
-  if (sj.nsplit <= FBN_SLAB_DIRECT) {
-    slab_direct(sj, gb - J.blk0[u]);
-    return;
-  }
+  if (sj.nsplit <= FBN_SLAB_DIRECT) return slab_direct(sj, gb - J.blk0[u]);
   const int qd = threadIdx.x & 63, grp = threadIdx.x >> 6;
   const size_t total = (size_t)sj.M * sj.N;
   const size_t i4 = (size_t)(gb - J.blk0[u]) * 64 + qd;   // output quad
@@ -1008,12 +1026,14 @@ __device__ __forceinline__ void slab_block(const SumJobs& J, int gb) {
     float* cp = sj.out + (size_t)m * sj.ldc + n + (n < sj.seg ? sj.off0 : sj.off1);
     if (sj.beta != 0.f) t += sj.beta * *reinterpret_cast<const f32x4*>(cp);
     *reinterpret_cast<f32x4*>(cp) = t;
+    return sq4(t);
   }
+  return 0.0;
 }
 // wide jobs (C >= FBN_SUM_WIDE): a block takes 16 consecutive columns and 16 row streams (16 lanes
 // read one 64-B run of a row: coalesced; every row stream has nch/16 rows), then a fixed-order fold
 // of the 16 streams
-__device__ __forceinline__ void sum_wide_block(const SumJob& jb, int c0) {
+__device__ __forceinline__ double sum_wide_block(const SumJob& jb, int c0) {
   __shared__ float red[16][17];
   const int col = threadIdx.x & 15, str = threadIdx.x >> 4, c = c0 + col;
   const size_t ld = jb.ld > 0 ? jb.ld : jb.C;
@@ -1033,23 +1053,20 @@ __device__ __forceinline__ void sum_wide_block(const SumJob& jb, int c0) {
 #pragma unroll
     for (int k = 0; k < 16; ++k) t += red[k][col];
     t *= jb.scale;
-    jb.out[c] = jb.beta != 0.f ? jb.beta * jb.out[c] + t : t;
+    t = jb.beta != 0.f ? jb.beta * jb.out[c] + t : t;
+    jb.out[c] = t;
+    return jb.sq ? (double)(t * t) : 0.0;
   }
+  return 0.0;
 }
-__global__ void __launch_bounds__(256) sum_jobs_kernel(SumJobs J) {
+__device__ __forceinline__ double sum_jobs_block(const SumJobs& J) {
   __shared__ float red[4];
   const int gc = blockIdx.x;
-  if (gc >= J.col0[J.n]) {
-    slab_block(J, gc - J.col0[J.n]);
-    return;
-  }
+  if (gc >= J.col0[J.n]) return slab_block(J, gc - J.col0[J.n]);
   int u = 0;
   while (u + 1 < J.n && gc >= J.col0[u + 1]) ++u;
   const SumJob jb = J.j[u];
-  if (jb.C >= FBN_SUM_WIDE) {
-    sum_wide_block(jb, (gc - J.col0[u]) * 16);
-    return;
-  }
+  if (jb.C >= FBN_SUM_WIDE) return sum_wide_block(jb, (gc - J.col0[u]) * 16);
   const int c = gc - J.col0[u];
   const size_t ld = jb.ld > 0 ? jb.ld : jb.C;
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
@@ -1065,8 +1082,41 @@ __global__ void __launch_bounds__(256) sum_jobs_kernel(SumJobs J) {
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) {
-    const float t = jb.scale * ((red[0] + red[1]) + (red[2] + red[3]));
-    jb.out[c] = jb.beta != 0.f ? jb.beta * jb.out[c] + t : t;
+    float t = jb.scale * ((red[0] + red[1]) + (red[2] + red[3]));
+    t = jb.beta != 0.f ? jb.beta * jb.out[c] + t : t;
+    jb.out[c] = t;
+    return jb.sq ? (double)(t * t) : 0.0;
+  }
+  return 0.0;
+}
+__global__ void __launch_bounds__(256) sum_jobs_kernel(SumJobs J) { (void)sum_jobs_block(J); }
+// fbn_sum_jobs_sq: the same sums, and the squares of the dense gradients into the norm slots (block
+// reduction and slot add in f64, as sumsq_norms_kernel)
+__global__ void __launch_bounds__(256) sum_jobs_sq_kernel(SumJobs J, SumSq Q) {
+  __shared__ double sred[4];
+  const int nsum = J.col0[J.n] + J.blk0[J.ns];
+  double acc = 0.0;
+  if ((int)blockIdx.x < nsum) {
+    acc = sum_jobs_block(J);
+  } else {
+    const int rb = blockIdx.x - nsum;
+    int u = 0;
+    while (u + 1 < Q.nr && rb >= Q.rblk0[u + 1]) ++u;
+    const SqRange r = Q.r[u];
+    const long long i0 = (long long)(rb - Q.rblk0[u]) * FBN_SQ_RANGE_BLOCK + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < FBN_SQ_RANGE_BLOCK / 256; ++k) {
+      const long long i = i0 + k * 256;
+      const float v = i < r.n ? r.x[i] : 0.f;
+      acc += (double)(v * v);
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double t = (sred[0] + sred[1]) + (sred[2] + sred[3]);
+    if (t != 0.0) atomicAdd(Q.out + (blockIdx.x & (FBN_SUMSQ_SLOTS - 1)), t);
   }
 }
 
@@ -1576,7 +1626,24 @@ extern "C" int fbn_row_chunks(int B) { return row_chunks(B); }
 // jobs: host array of n (<= 16) {part, out, nch, C, scale, beta, ld, pad} (copied into the kernel
 // argument); slabs: host array of ns (<= 8) {ws, out, M, N, ldc, nsplit, seg, off0, off1, beta}
 // (N, ldc, seg, off0, off1 multiples of 4; out 16-B aligned).  One launch for both.
+static int sum_jobs_impl(const SumJob* jobs, int n, const SlabJob* slabs, int ns, const SqRange* ranges, int nr,
+                         double* sumsq, void* stream);
 extern "C" int fbn_sum_jobs2(const SumJob* jobs, int n, const SlabJob* slabs, int ns, void* stream) {
+  return sum_jobs_impl(jobs, n, slabs, ns, nullptr, 0, nullptr, stream);
+}
+// fbn_sum_jobs2 with the clip norm's dense part: the squares of the outputs of the sum jobs with sq = 1
+// and of every slab job, and of the nr (<= 24) ranges {pointer, count} (host array; dense gradients this
+// launch does not produce, final before it), added to the norm slots sumsq[FBN_SUMSQ_SLOTS] in f64.
+extern "C" int fbn_sum_jobs_sq(const SumJob* jobs, int n, const SlabJob* slabs, int ns, const SqRange* ranges, int nr,
+                               double* sumsq, void* stream) {
+  if (!sumsq || nr < 0 || nr > FBN_MAX_SQ_RANGES || (nr > 0 && !ranges)) {
+    fbn_set_error("fbn_sum_jobs_sq: sumsq and at most 24 ranges");
+    return FBN_ERR_ARG;
+  }
+  return sum_jobs_impl(jobs, n, slabs, ns, ranges, nr, sumsq, stream);
+}
+static int sum_jobs_impl(const SumJob* jobs, int n, const SlabJob* slabs, int ns, const SqRange* ranges, int nr,
+                         double* sumsq, void* stream) {
   if (n < 0 || ns < 0 || n > FBN_MAX_SUM_JOBS || ns > FBN_MAX_SLAB_JOBS) {
     fbn_set_error("fbn_sum_jobs2: too many jobs");
     return FBN_ERR_ARG;
@@ -1603,6 +1670,24 @@ extern "C" int fbn_sum_jobs2(const SumJob* jobs, int n, const SlabJob* slabs, in
     J.blk0[i + 1] = J.blk0[i] + (int)fbn_cdiv((long long)sj.M * sj.N / 4, qpb);
   }
   const int blocks = J.col0[n] + J.blk0[ns];
+  if (sumsq) {
+    SumSq Q;
+    Q.out = sumsq;
+    Q.nr = nr;
+    Q.rblk0[0] = 0;
+    for (int i = 0; i < nr; ++i) {
+      if (!ranges[i].x || ranges[i].n < 0) {
+        fbn_set_error("fbn_sum_jobs_sq: null range");
+        return FBN_ERR_ARG;
+      }
+      Q.r[i] = ranges[i];
+      Q.rblk0[i + 1] = Q.rblk0[i] + (int)fbn_cdiv(ranges[i].n, (long long)FBN_SQ_RANGE_BLOCK);
+    }
+    if (blocks + Q.rblk0[nr] <= 0) return FBN_OK;
+    fbn_launch(sum_jobs_sq_kernel, dim3(blocks + Q.rblk0[nr]), dim3(256), 0, (hipStream_t)stream, J, Q);
+    FBN_CHECK_LAUNCH();
+    return FBN_OK;
+  }
   if (blocks <= 0) return FBN_OK;
   fbn_launch(sum_jobs_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, J);
   FBN_CHECK_LAUNCH();

@@ -357,6 +357,7 @@ __global__ void claim_rows_kernel(const int64_t* __restrict__ item, const int64_
 //    claimers that find no slot, add straight to global memory.
 template <int D>
 __global__ void __launch_bounds__(FBN_FOLD_THREADS) sparse_fixup_dup_kernel(const int* __restrict__ dup, int n, GradSrc s) {
+  resolve_src(s);
   constexpr int NPL = D / 64 > 0 ? D / 64 : 1;   // floats per lane of a row
   constexpr int MAXV = 16;                        // distinct vectors of a wave chunk (2 per sample)
   constexpr int CPW = FBN_FOLD_CHUNKS;            // 64-entry chunks per wave
@@ -486,6 +487,7 @@ __device__ __forceinline__ long long to_fx(float x) { return __double2ll_rn((dou
 template <int D>
 __global__ void __launch_bounds__(256) sparse_fold_fx_kernel(const int* __restrict__ dup, int* __restrict__ hasdup,
                                                              int n, GradSrc s, unsigned long long* __restrict__ acc) {
+  resolve_src(s);
   const int lane = threadIdx.x & 63;
   for (long long e0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) - lane; e0 < n;
        e0 += (long long)gridDim.x * blockDim.x) {
@@ -518,6 +520,7 @@ template <int D>
 __global__ void __launch_bounds__(256) sumsq_norms_kernel(GradSrc s, const double* __restrict__ gnorm, int n,
                                                           double* __restrict__ out, unsigned long long* __restrict__ fx,
                                                           const float* __restrict__ dense, long long n_dense) {
+  resolve_src(s);
   __shared__ double red[4];
   const int lane = threadIdx.x & 63;
   double acc = 0.0;
@@ -1990,9 +1993,10 @@ __device__ __forceinline__ void adam_commit_body(float* __restrict__ p, float* _
                                                  long long nblk) {
   constexpr int G = D / 4, RPW = 64 / G;
   // ring copy of this step's per-sample vectors (N > 1, per-entry rows: the rows were received
-  // straight into the ring slot -- nothing to copy)
-  if (gs.Lp1 > 1) {
-    float* dst = const_cast<float*>(ps.ring) + (size_t)(t % ps.ring_n) * ps.ring_stride;
+  // straight into the ring slot -- nothing to copy; nor when the backward wrote them there itself,
+  // fbn_fields_bwd_slot: the source IS the slot)
+  float* dst = const_cast<float*>(ps.ring) + (size_t)(t % ps.ring_n) * ps.ring_stride;
+  if (gs.Lp1 > 1 && gs.vec != dst) {
     const long long n4 = (long long)B * 2 * D / 4, st = nblk * blockDim.x;
     for (long long i0 = bid * blockDim.x + threadIdx.x; i0 < n4; i0 += 8 * st) {   // 8 loads in flight
       f32x4 x[8];

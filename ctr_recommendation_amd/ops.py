@@ -213,6 +213,10 @@ _DEFER_REDUCE = os.environ.get("FBN_DEFER_REDUCE", "1") != "0"
 _WGRAD_GROUP = os.environ.get("FBN_WGRAD_GROUP", "1") != "0"
 
 
+class _SqRange(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_void_p), ("n", ctypes.c_longlong)]
+
+
 class _SlabGemm(ctypes.Structure):
     _fields_ = [("A", ctypes.c_void_p), ("B", ctypes.c_void_p), ("ws", ctypes.c_void_p), ("ws_bytes", ctypes.c_size_t),
                 ("A2", ctypes.c_void_p), ("B2", ctypes.c_void_p), ("M", ctypes.c_int), ("N", ctypes.c_int),
@@ -312,20 +316,71 @@ class DeferredSums:
 
     timed_group = False
 
-    def flush(self, stream, probe: Optional[Dict[str, list]] = None):
+    def classify(self, grads: Dict[str, torch.Tensor]):
+        """For the clip norm inside the flush (flush(sumsq=...)): each dense gradient by key -- covered
+        when its tensor is the `out` of a sum or slab job of this flush (that job's blocks square what
+        they write; the sum job is marked sq), otherwise on the range list.  Returns (ranges, partial):
+        ranges [(pointer, count)], partial [(key, N, remap)] the slab outputs whose job writes only some
+        columns (mlp.0.weight: 15d of 21d through wa_remap) -- the others must hold zeros."""
+        by_ptr = {t.data_ptr(): (k, t) for k, t in grads.items()}
+        covered, partial = set(), []
+        for i, j in enumerate(self.jobs):
+            hit = by_ptr.get(j[1])
+            if hit is None:
+                continue                    # not a gradient (the mean loss)
+            if j[3] != hit[1].numel() or j[5] != 0.0 or hit[0] in covered:
+                raise RuntimeError("clip norm in the sum launch: a sum job must write one whole dense gradient, once")
+            covered.add(hit[0])
+            self.jobs[i] = j[:7] + (1,)
+        for sj in self.slabs:
+            hit = by_ptr.get(sj[1])
+            if hit is None or hit[0] in covered:
+                raise RuntimeError("clip norm in the sum launch: a slab job's output is not one dense gradient")
+            covered.add(hit[0])
+            if sj[2] * sj[3] != hit[1].numel():
+                partial.append((hit[0], sj[3], (sj[6], sj[7], sj[8])))
+        ranges = [(t.data_ptr(), t.numel()) for k, t in grads.items() if k not in covered]
+        return ranges, partial
+
+    def flush(self, stream, probe: Optional[Dict[str, list]] = None, sumsq: Optional[torch.Tensor] = None,
+              grads: Optional[Dict[str, torch.Tensor]] = None):
+        """sumsq (with grads, the dense gradients by key): the launch also adds the squares of every
+        dense gradient to the norm slots (fbn_sum_jobs_sq; see classify) -- returns classify's partial."""
         # the bench's "wgrad_group" events time the launch of the step's weight gradients: the early one
         # when the trainer launched it beside the fields backward, else this one
         self.launch_group(stream, None if self.timed_group else probe)
+        ranges, partial = self.classify(grads) if sumsq is not None else (None, None)
         jobs, slabs = self.jobs, self.slabs
-        while jobs or slabs:
+        while jobs or slabs or ranges:
             jc, sc = jobs[:16], slabs[:8]
             jobs, slabs = jobs[16:], slabs[8:]
             arr = (_SumJob * max(1, len(jc)))(*[_SumJob(*j) for j in jc])
             sarr = (_SlabJob * max(1, len(sc)))(*[_SlabJob(*j) for j in sc])
+            if sumsq is not None:
+                rc, ranges = ranges[:24], ranges[24:]
+                rarr = (_SqRange * max(1, len(rc)))(*[_SqRange(*r) for r in rc])
+                _lib.keep((arr, sarr, rarr))
+                call("fbn_sum_jobs_sq", ctypes.addressof(arr), len(jc), ctypes.addressof(sarr), len(sc),
+                     ctypes.addressof(rarr), len(rc), ptr(sumsq), stream)
+                continue
             _lib.keep((arr, sarr))
             call("fbn_sum_jobs2", ctypes.addressof(arr), len(jc), ctypes.addressof(sarr), len(sc), stream)
         self.jobs, self.slabs, self.keep = [], [], []
         self.used = set()
+        return partial
+
+
+def check_unwritten_columns_zero(gt: torch.Tensor, N: int, remap) -> None:
+    """A slab job writes compact columns [0, N) of gt's rows through remap (seg, off0, off1); the clip
+    norm in the sum launch counts only those, so the other columns must hold zeros (mlp.0.weight: the
+    columns of V_0 and the (0, j) pairs, whose inputs are zero).  Synchronises: run once, not per step."""
+    seg, off0, off1 = remap
+    cols = torch.arange(N, device=gt.device)
+    keep = torch.ones(gt.shape[1], dtype=torch.bool, device=gt.device)
+    keep[cols + torch.where(cols < seg, off0, off1)] = False
+    worst = gt[:, keep].abs().max().item() if bool(keep.any()) else 0.0
+    if worst != 0.0:
+        raise RuntimeError(f"dense gradient columns outside the slab job's image are not zero (max {worst})")
 
 
 def colsum(X, B, C, ldx, out, beta=0.0, stream=None):
@@ -740,16 +795,22 @@ class _SideWork:
 def backward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], a: Dict[str, torch.Tensor],
              gout: torch.Tensor, g: Dict[str, torch.Tensor], cfg: FwdConfig, *,
              table_grad: Optional[torch.Tensor] = None, gvec: Optional[torch.Tensor] = None,
-             gnorm: Optional[torch.Tensor] = None,
+             gnorm: Optional[torch.Tensor] = None, gslot=None, dense_sumsq: Optional[torch.Tensor] = None,
              pos: Optional[torch.Tensor] = None,
              sendbuf: Optional[torch.Tensor] = None, coll: Collective = NO_COLLECTIVE,
              ntot: Optional[int] = None, extra_sums=(), side: Optional["torch.cuda.Stream"] = None,
-             probe: Optional[Dict[str, list]] = None, hooks: Optional[Dict[str, object]] = None) -> None:
+             probe: Optional[Dict[str, list]] = None, hooks: Optional[Dict[str, object]] = None):
     """Backward from dL/dlogit (gout [B]) into the gradient buffers ``g`` (same keys as ``p``).
 
     table_grad: dense [V, d] (drop-in, accumulated by atomics); or gvec [B, 2, d] (native
     trainer: per-sample {item-row grad, history-row grad}, resolved through the slot map)
     (native trainer); in multi-GPU mode (pos given) rows are written to sendbuf instead.
+    gslot (instead of gvec): (ring, ring_n, ring_stride, step, cell) -- the per-sample vectors go
+    straight into deferred-gradient ring slot step % ring_n, chosen on the device, and the slot's
+    address to the pointer cell (fbn_fields_bwd_slot).
+    dense_sumsq: the clip norm's slots -- the squares of every gradient in ``g`` are added to them by
+    the backward's sum launch (DeferredSums.flush(sumsq=...)); returns the partially written slab
+    outputs, whose other columns the caller checks to be zero (else None).
     Every g[...] buffer is overwritten (not accumulated), except the table gradient which is
     accumulated into (callers zero it).
     extra_sums: further (part, nch, C, out[, scale, beta]) reductions to finalise in the same
@@ -993,14 +1054,24 @@ def backward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], a: Dict
         _lib.keep(outs_arr)
         outs = ctypes.cast(outs_arr, ctypes.c_void_p).value
     evb = _probe_start(probe, "fields_bwd")     # bench / tools: the fields backward
-    call("fbn_fields_bwd_img" if s3img else "fbn_fields_bwd", ptr(batch["item_id"]), ptr(seq) if Lr else None,
-         ptr(batch["likes_level"]),
-         ptr(batch["views_level"]), ptr(a["hmm"]), ptr(p["mm_proj.1.weight"]), ptr(p["mm_proj.1.bias"]), LN_EPS,
-         ptr(p["senet.excitation.0.weight"]), ptr(p["senet.excitation.0.bias"]), ptr(p["senet.excitation.2.weight"]),
-         R, ncate, ptr(p["cate_emb.weight"]), ptr(a["X"]), ptr(a["a"]), ptr(a["cnt"]), ptr(dV), ptr(dhmm),
-         ptr(dhs if s3img else dhmm16), ptr(partials), outs,
-         ptr(table_grad), ptr(gvec), ptr(gnorm), V, ptr(pos), ptr(sendbuf),
-         int(sendbuf is not None and sendbuf.dtype == torch.bfloat16), B, Lr, d, st)
+    if gslot is not None:
+        ring, ring_n, ring_stride, step, cell = gslot
+        call("fbn_fields_bwd_slot", ptr(batch["item_id"]), ptr(seq) if Lr else None, ptr(batch["likes_level"]),
+             ptr(batch["views_level"]), ptr(a["hmm"]), ptr(p["mm_proj.1.weight"]), ptr(p["mm_proj.1.bias"]), LN_EPS,
+             ptr(p["senet.excitation.0.weight"]), ptr(p["senet.excitation.0.bias"]),
+             ptr(p["senet.excitation.2.weight"]), R, ncate, ptr(p["cate_emb.weight"]), ptr(a["X"]), ptr(a["a"]),
+             ptr(a["cnt"]), ptr(dV), ptr(dhmm), ptr(dhs if s3img else dhmm16), int(bool(s3img)), ptr(partials), outs,
+             ptr(ring), ring_n, ring_stride, ptr(step), ptr(cell), ptr(gnorm), V, B, Lr, d, st)
+    else:
+        call("fbn_fields_bwd_img" if s3img else "fbn_fields_bwd", ptr(batch["item_id"]), ptr(seq) if Lr else None,
+             ptr(batch["likes_level"]),
+             ptr(batch["views_level"]), ptr(a["hmm"]), ptr(p["mm_proj.1.weight"]), ptr(p["mm_proj.1.bias"]), LN_EPS,
+             ptr(p["senet.excitation.0.weight"]), ptr(p["senet.excitation.0.bias"]),
+             ptr(p["senet.excitation.2.weight"]),
+             R, ncate, ptr(p["cate_emb.weight"]), ptr(a["X"]), ptr(a["a"]), ptr(a["cnt"]), ptr(dV), ptr(dhmm),
+             ptr(dhs if s3img else dhmm16), ptr(partials), outs,
+             ptr(table_grad), ptr(gvec), ptr(gnorm), V, ptr(pos), ptr(sendbuf),
+             int(sendbuf is not None and sendbuf.dtype == torch.bfloat16), B, Lr, d, st)
     _probe_end(evb)
     if hooks and "after_fields_bwd" in hooks:     # N > 1: the gradient rows are complete -> exchange
         hooks["after_fields_bwd"]()
@@ -1023,5 +1094,8 @@ def backward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], a: Dict
         sums.add(*job)
     if hooks and "before_flush" in hooks:         # trainer: join the early weight-gradient launch
         hooks["before_flush"]()
-    sums.flush(st, probe)
+    if dense_sumsq is not None and side is not None:
+        raise ValueError("dense_sumsq needs the weight gradients on the main stream (side=None)")
+    partial = sums.flush(st, probe, sumsq=dense_sumsq, grads=g if dense_sumsq is not None else None)
     wg.join()
+    return partial

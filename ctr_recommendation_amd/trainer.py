@@ -125,6 +125,17 @@ _OWNER_CLAIM_FUSED = os.environ.get("FBN_OWNER_CLAIM_FUSED", "1") != "0"
 # fbn_sparse_fixup (A/B)
 _SHARD_W16_SIDE = os.environ.get("FBN_SHARD_W16_SIDE", "1") != "0"
 _OWNER_FOLD = os.environ.get("FBN_OWNER_FOLD", "1") != "0"
+# single GPU, deferred table gradients: the fields backward writes the step's per-sample vectors straight
+# into their deferred-gradient ring slot (fbn_fields_bwd_slot) and every reader takes them there through
+# the pointer cell, so the step tail copies nothing; FBN_GVEC_SLOT=0 keeps the separate gvec buffer and
+# the tail's ring copy (A/B; bit-identical, tests/test_gpu_ring_slot.py)
+_GVEC_SLOT = os.environ.get("FBN_GVEC_SLOT", "1") != "0"
+# single GPU, float-atomic mode: the clip norm off the main stream -- the dense gradients' squares come out
+# of the backward's sum launch (fbn_sum_jobs_sq) and the table part (fbn_sumsq_sparse_norms, table only)
+# follows the duplicate fold on whichever stream runs it, so no norm launch stands between the sum launch
+# and the step tail; FBN_NORM_IN_SUMS=0 keeps the norm launch after the sum launch (A/B; the same norm to
+# f64 addition order, tests/test_gpu_norm_in_sums.py).  Deterministic mode keeps its own chain
+_NORM_IN_SUMS = os.environ.get("FBN_NORM_IN_SUMS", "1") != "0"
 # debug: after every record_program, check that no tensor of the trainer's persistent state lies in the
 # recording pool (check_program_memory; the tests run it explicitly)
 _CHECK_POOL = os.environ.get("FBN_CHECK_POOL", "0") == "1"
@@ -471,6 +482,9 @@ class FiBiNETTrainer:
         self._fc_seen = 0
         self._fc_steps = 0
         self.ring_cell = torch.zeros(2, dtype=torch.int64, device=dev)     # fbn_ring_slot's pointer cell
+        self.gvec_slot = _GVEC_SLOT and not sharded and self.deferred       # fbn_fields_bwd_slot (with L > 0)
+        self.norm_in_sums = _NORM_IN_SUMS and _DENSE_SUMSQ_FOLD and not sharded and not self.deterministic
+        self._gap_checked = False   # norm_in_sums: the unwritten columns of mlp.0.weight's gradient seen zero
         self._fc_grad = None        # fixed-capacity rows, f32, when they are not deferred
         self._fc_extra = None       # fixed-capacity form: duplicates' sums per claimer (zero at rest)
         self._fc_part = None        # ... and fbn_owner_fold's per-workgroup sums of squares
@@ -739,6 +753,16 @@ class FiBiNETTrainer:
                                                                         and not torch.cuda.is_current_stream_capturing()))
                       and not self.deterministic and L > 0
                       and not self._early_grad_xchg())
+        # the step's per-sample vectors: gvec, or (gvec_slot) ring slot step % ring_n, which the fields
+        # backward chooses on the device -- its readers then go through the pointer cell
+        slot = self.gvec_slot and self.xchg is None and L > 0
+        gv, gcell = (self.ring_cell, FBN_GRAD_CELL) if slot else (self.gvec, 0)
+        in_sums = self.norm_in_sums and self.xchg is None and L > 0
+
+        def table_norm(stream):
+            # (in_sums) the table part of the clip norm, right after the fold, on the fold's stream
+            call("fbn_sumsq_sparse_norms", ptr(self.gnorm), ptr(gv), ptr(self.extra), ptr(self.slot_row),
+                 (L + 1) | gcell, B * (L + 1), d, ptr(self.sumsq), None, None, 0, stream)
         if (self.xchg is not None and self.shard_graph and probe is None and masks_out is None
                 and self.table_adam != "eager" and not self._recording):
             sendbuf = self.xchg.make_sendbuf()
@@ -759,8 +783,10 @@ class FiBiNETTrainer:
             if fixup_side:
                 def fork_fixup():
                     _lib.wait_stream(self.side, main)
-                    call("fbn_sparse_fixup_dup", ptr(self.dup), B * (L + 1), ptr(self.gvec), ptr(self.extra),
-                         ptr(self.slot_row), L + 1, d, self.side.cuda_stream)
+                    call("fbn_sparse_fixup_dup", ptr(self.dup), B * (L + 1), ptr(gv), ptr(self.extra),
+                         ptr(self.slot_row), (L + 1) | gcell, d, self.side.cuda_stream)
+                    if in_sums:
+                        table_norm(self.side.cuda_stream)
                 bhooks = {"after_fields_bwd": fork_fixup}
                 if _WGRAD_EARLY and cfg.bf16:
                     def early_wgrad(sums):
@@ -768,11 +794,19 @@ class FiBiNETTrainer:
                         sums.launch_group(self.side.cuda_stream, probe, tstream=self.side)
                     bhooks["after_bilinear_bwd"] = early_wgrad
                     bhooks["before_flush"] = lambda: _lib.wait_stream(main, self.side)
-            ops.backward(self.p, batch, a, a["gout"], self.g, cfg, gvec=self.gvec if self.xchg is None else None,
+            gaps = ops.backward(self.p, batch, a, a["gout"], self.g, cfg,
+                         dense_sumsq=self.sumsq if in_sums else None,
+                         gvec=self.gvec if self.xchg is None and not slot else None,
+                         gslot=(self.ring, self.ring_n, self._ring_stride(), self.step_dev, self.ring_cell)
+                         if slot else None,
                          gnorm=self.gnorm if self.xchg is None else None,
                          pos=pos, sendbuf=sendbuf, coll=self.bn_coll, ntot=self._bn_n(ntot, B),
                          extra_sums=[(a["loss_terms"], B, 1, self.loss, 1.0 / ntot)], probe=probe,
                          hooks=bhooks)
+            if gaps and not self._gap_checked and not torch.cuda.is_current_stream_capturing():
+                for key, ncols, remap in gaps:      # once: a synchronising check
+                    ops.check_unwritten_columns_zero(self.g[key], ncols, remap)
+                self._gap_checked = True
         dense_work = None
         if self.sharded and self._early_grad_xchg() and self.native_comm is None and not self.coll.det:
             # the dense gradients are final once the compute is: their all-reduce goes out now,
@@ -795,17 +829,19 @@ class FiBiNETTrainer:
                 if L == 0:
                     raise ValueError("deterministic mode needs the item_seq history (L > 0)")
                 # extra[claimer] becomes the FULL row gradient (Lp1 | FBN_GRAD_FULL for the readers)
-                gsrc = (self.gvec, self.extra, (L + 1) | FBN_GRAD_FULL)
-                call("fbn_sparse_fold_fx", ptr(self.dup), ptr(self.hasdup), n_ent, ptr(self.gvec), ptr(self.slot_row),
+                gsrc = (gv, self.extra, (L + 1) | FBN_GRAD_FULL | gcell)
+                call("fbn_sparse_fold_fx", ptr(self.dup), ptr(self.hasdup), n_ent, ptr(gv), ptr(self.slot_row),
                      gsrc[2], d, ptr(self.fx), st)
             else:
-                gsrc = (self.gvec, self.extra, L + 1)
+                gsrc = (gv, self.extra, (L + 1) | gcell)
                 if fixup_side:
                     _lib.wait_stream(main, self.side)     # the fold (and the side's table passes) done
                     joined = True
                 else:
-                    call("fbn_sparse_fixup_dup", ptr(self.dup), n_ent, ptr(self.gvec), ptr(self.extra),
-                         ptr(self.slot_row), L + 1, d, st)
+                    call("fbn_sparse_fixup_dup", ptr(self.dup), n_ent, ptr(gv), ptr(self.extra),
+                         ptr(self.slot_row), gsrc[2], d, st)
+                    if in_sums:
+                        table_norm(st)
         else:
             # owner: one received row per entry -- straight into this step's deferred-gradient ring
             # slot when it fits, else a buffer of its own and the rows applied at the step end
@@ -877,7 +913,9 @@ class FiBiNETTrainer:
         # clip_grad_norm_(10): dense grads (identical on every rank) + disjoint table shards
         tab_acc = self.sumsq_tab if self.sharded else self.sumsq
         dense_done = False
-        if self.xchg is None and L > 0:
+        if in_sums:
+            dense_done = True      # both parts are in the slots (or on their way: the side stream is joined)
+        elif self.xchg is None and L > 0:
             # one process: the dense gradients are final here, so their squares ride along
             fold = not self.sharded and _DENSE_SUMSQ_FOLD
             call("fbn_sumsq_sparse_norms", ptr(self.gnorm), ptr(gsrc[0]), ptr(gsrc[1]), ptr(self.slot_row), gsrc[2],

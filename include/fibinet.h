@@ -176,6 +176,18 @@ int fbn_fields_bwd_img(const int64_t* item_id, const int64_t* item_seq, const in
                        const float* a, const float* cnt, const float* dV, float* dhmm, void* dhmm_img,
                        float* partials, float* const* param_grads, float* gtab, float* gvec, double* gnorm,
                        long long V, const int* pos, void* sendbuf, int send_bf16, int B, int L, int D, void* stream);
+/* The single-GPU trainer's form: the per-sample vectors go straight into deferred-gradient ring slot
+ * *step % ring_n of ring [ring_n][ring_stride] (ring_stride >= B*2*D floats; the slot is chosen on the
+ * device, so a recorded step program or a captured graph replays fixed arguments) and the slot's
+ * address to *cell.  The fold, the norm and the step tail read them there (cell with
+ * Lp1 | FBN_GRAD_CELL), and fbn_adam_step_tail / fbn_adam_commit skip their ring copy because the
+ * source is the slot.  dhmm_is_img: dhmm16 holds split images as fbn_fields_bwd_img's dhmm_img. */
+int fbn_fields_bwd_slot(const int64_t* item_id, const int64_t* item_seq, const int64_t* likes, const int64_t* views,
+                        const float* hmm, const float* ln_g, const float* ln_b, float ln_eps, const float* w1,
+                        const float* b1, const float* w2, int R, int n_cate, const float* cate, const float* X,
+                        const float* a, const float* cnt, const float* dV, float* dhmm, void* dhmm16, int dhmm_is_img,
+                        float* partials, float* const* param_grads, float* ring, int ring_n, long long ring_stride,
+                        const int* step, void* cell, double* gnorm, long long V, int B, int L, int D, void* stream);
 /* gnorm (optional, with gvec): [B][2] float64 sums of squares of the two per-sample vectors,
  * read by fbn_sumsq_sparse_norms for the clip_grad_norm_ total (src/train_fibinet.py:119).
  * pos / sendbuf (N > 1): one gradient row per routed entry, f32, or bf16 when send_bf16 (the bf16
@@ -294,6 +306,13 @@ int fbn_colsum_partial(const float* X, int B, int C, int ldx, float* part, void*
  * remap multiples of 4, buffers 16-B aligned). */
 int fbn_sum_jobs(const void* jobs, int n, void* stream);
 int fbn_sum_jobs2(const void* jobs, int n, const void* slabs, int ns, void* stream);
+/* fbn_sum_jobs2 with the dense part of the clip norm (src/train_fibinet.py:119) in the same launch:
+ * every block adds the squares of the outputs it has just written -- the sum jobs whose last field (pad)
+ * is 1, every slab job -- to the norm slots sumsq[FBN_SUMSQ_SLOTS] (f64 block reduction and slot add),
+ * and extra blocks square nr <= 24 ranges {const float* x; long long n;} (host array): dense gradients
+ * the launch does not produce, final before it. */
+int fbn_sum_jobs_sq(const void* jobs, int n, const void* slabs, int ns, const void* ranges, int nr, double* sumsq,
+                    void* stream);
 
 /* ---------------------------------------------------------------- K7 head: Linear(256,1)+sigmoid+BCE
  * Replaces src/model_fibinet.py:134,136,199 and nn.BCELoss fwd/bwd (src/train_fibinet.py:79,115). */

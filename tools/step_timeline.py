@@ -1,10 +1,12 @@
 """Per-step timeline of bench.py's graph replays from a rocprofv3 kernel_trace.csv (lazy table Adam).
 
-  python tools/step_timeline.py run_kernel_trace.csv [--steps N] [--verbose]
+  python tools/step_timeline.py run_kernel_trace.csv [--steps N] [--verbose] [--side NAME[,NAME...]]
 
 Steps are split at claim_rows_kernel (or, fused, the claimed-row adam_catchup).  The rolling-window Adam replay (adam_catchup on 256
 workgroups) and the next-batch prefetch (adam_prefetch) run on the side stream ("window" below:
-their span); every other kernel is on the main stream.  Prints, per step,
+their span); every other kernel is on the main stream (--side: further kernel-name substrings that
+run on the side stream in the traced build, e.g. sumsq_norms once the clip norm's table part follows
+the fold there).  Prints, per step,
 the span, the main stream's busy time and idle gaps, the window's span, and (--verbose) the
 kernels in order with their durations and how much of each overlapped the window.
 """
@@ -30,11 +32,13 @@ def main():
     # steps of the run being studied (bench.py also times an fp32 run: its GEMMs are gemm_kernel)
     starts = [s for j, s in enumerate(starts[:-1]) if any(match in e[2] for e in ev[s:starts[j + 1]])] + starts[-1:]
 
+    side = tuple(sys.argv[sys.argv.index("--side") + 1].split(",")) if "--side" in sys.argv else ()
+
     def is_window(k, ks):
         # side stream: the rolling-window replay (the adam_catchup launch of the step with the
         # smaller grid) and the next batch's ahead-of-time catch-up (adam_prefetch)
         if any(s in k[2] for s in ("adam_prefetch", "adam_pretag", "adam_window2",
-                                   "sparse_fixup_dup")):
+                                   "sparse_fixup_dup") + side):
             return True
         cs = [c[3] for c in ks if "adam_catchup" in c[2]]
         return "adam_catchup" in k[2] and len(cs) > 1 and k[3] == min(cs)

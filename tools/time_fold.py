@@ -23,6 +23,8 @@ _lib.call("fbn_claim_rows", _lib.ptr(bs[1][0]["item_id"]), _lib.ptr(bs[1][0]["it
           _lib.ptr(tr.slot_row), _lib.ptr(tr.dup), None, _lib.stream_handle(dev))
 torch.cuda.synchronize()
 n = B * (L + 1)
+# the step's per-sample vectors: the trainer's gvec buffer, or (the default) the step's ring slot
+gvec = tr.ring[(tr.host_step - 1) % tr.ring_n] if tr.gvec_slot else tr.gvec
 ndup = int((tr.dup[:n] >= 0).sum())
 st = _lib.stream_handle(dev)
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -30,7 +32,7 @@ for mode in ("0",):
     for it in range(2):
         e0.record()
         for _ in range(10):
-            _lib.call("fbn_sparse_fixup_dup", _lib.ptr(tr.dup), n, _lib.ptr(tr.gvec), _lib.ptr(tr.extra),
+            _lib.call("fbn_sparse_fixup_dup", _lib.ptr(tr.dup), n, _lib.ptr(gvec), _lib.ptr(tr.extra),
                       _lib.ptr(tr.slot_row), L + 1, d, st)
         e1.record()
         torch.cuda.synchronize()
