@@ -518,7 +518,6 @@ def forward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], cfg: Fwd
             masks_out: Optional[Dict[str, torch.Tensor]] = None, acts: Optional[Dict[str, torch.Tensor]] = None,
             probe: Optional[Dict[str, list]] = None, masks_in: Optional[Dict[str, torch.Tensor]] = None,
             after_gather=None, count_batches: bool = True, w16_ready: bool = False,
-            hooks: Optional[Dict[str, object]] = None,
             fields: Optional[FieldsStage] = None) -> Dict[str, torch.Tensor]:
     """Run the forward; returns the activation dict (probs, logits and what backward needs).
 
@@ -567,10 +566,6 @@ def forward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], cfg: Fwd
         hmm = buf("hmm", (B, d))
         gemm(w16["x"] if g16 else x_mm, w16["Wp"] if g16 else p["mm_proj.0.weight"], hmm, B, d, 128, 128, 128, d,
              False, True, bias=p["mm_proj.0.bias"], bf16=g16, stream=st)
-    if hooks and "after_mmproj" in hooks:         # trainer: side-stream work forked here
-        hooks["after_mmproj"]()
-    if hooks and "before_gather" in hooks:        # trainer: the table rows' claims ran on the side stream
-        hooks["before_gather"]()
     X = buf("X", (B, 2, d)) if fields is None else None   # fields 3 and 5 (the backward recomputes 1, 2, 4)
     # bf16 mode: the fields after SENET exist only as bf16 (GEMM operand and pair-kernel input)
     v16 = bf and not cfg.bilinear_each
@@ -638,8 +633,6 @@ def forward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], cfg: Fwd
     _probe_end(ev)
     if after_gather is not None:
         after_gather()
-    if hooks and "after_fields" in hooks:         # trainer: side-stream work forked here
-        hooks["after_fields"]()
     # bilinear: U = V W  ("all")  or  U_i = V_i W_i ("each"), then pair products into c
     fused_bil = bf and not cfg.bilinear_each and fused_bilinear(d)
     a["fused_bilinear"] = fused_bil
@@ -698,8 +691,6 @@ def forward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], cfg: Fwd
         gemm(c, p["mlp.0.weight"], h1pre, B, H1, KC, KC, 21 * d, H1, False, True, bias=p["mlp.0.bias"],
              rB=wa_remap(d), stream=st, stats=t1)
     _probe_end(ev1)
-    if hooks and "after_mlp0" in hooks:           # trainer: side-stream work forked here
-        hooks["after_mlp0"]()
     mean1, inv1 = buf("mean1", (H1,)), buf("inv1", (H1,))
     mean2, inv2 = buf("mean2", (H2,)), buf("inv2", (H2,))
     h1 = buf("h1", (B, H1))

@@ -24,7 +24,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -35,50 +35,12 @@ from ._lib import call, ptr
 from .exchange import DistCollective, NativeComm, RowExchange, native_comm_wanted
 from .model_fibinet import build_model
 
-# single GPU, bf16: where the step's bf16 weight images are made (A/B knob) -- "main": on the
-# main stream before the row claims; "side": on the side stream beside them; "late": on the side
-# stream, captured after the claimed-row catch-up
-_W16_MODE = os.environ.get("FBN_W16", "main")
-# single GPU: the side-stream table-Adam passes (window + next-batch prefetch) forked after the
-# MLP's first GEMM instead of right after the row claims (A/B knob)
-_SIDE_AFTER_MLP0 = os.environ.get("FBN_SIDE_AFTER_MLP0", "0") == "1"
-# ... or after the step's first GEMM (mm_proj), so a replayed graph launches that GEMM before the
-# side-stream branch (A/B knob)
-_SIDE_AFTER_MMPROJ = os.environ.get("FBN_SIDE_AFTER_MMPROJ", "0") == "1"
-# single GPU, A/B knobs of the stream placement (tools/ab_step.py, in-process: each measured SLOWER
-# than the default, profiles/r03_stream_placement_ab.txt):
-#   FBN_CLAIM_ON_SIDE=1  the row claims + claimed-row catch-up on the side stream from the step's
-#                        start, beside the bf16 weight images and the mm_proj GEMM (+15 us/step)
-#   FBN_FIXUP_ON_SIDE=1  the duplicate-gradient fold on the side stream after the fields backward
-#                        (round 3's first half: +2-3 us; since the weight gradients run as one grouped
-#                        launch after the fields backward the fold hides beside it: 0.4290 vs 0.4321
-#                        ms/step, profiles/r03s2_group_knobs_ab.txt -- so "auto", the default, puts it
-#                        there whenever the side stream is in use)
-#                        (+2-3 us/step)
-#   FBN_SIDE_SERIAL=1    the rolling window + next-batch prefetch on the main stream, in sequence
-#                        (0.5128 vs 0.4629 ms/step at C3: the overlap is worth 50 us there)
-# FBN_SIDE_SERIAL defaults to "auto": in sequence on the main stream below d = 128, where the side
-# work is small and the cross-queue edges cost more than the overlap saves (C2, graph-replayed:
-# 0.2833-0.2844 vs 0.2934-0.2952 ms/step; eager 0.30 vs 0.45-0.50, the host's event waits gone;
-# profiles/r03s2_side_serial_ab.txt), on the side stream from d = 128 on and in step programs
-_CLAIM_ON_SIDE = os.environ.get("FBN_CLAIM_ON_SIDE", "0") == "1"
-# single GPU, lazy table Adam, images on main: the bf16 image conversion rides in the row claims'
-# launch (FBN_HEAD_CONV=0: its own launch ahead of the claims, A/B)
-_HEAD_CONV = os.environ.get("FBN_HEAD_CONV", "1") != "0"
-_SIDE_SERIAL = os.environ.get("FBN_SIDE_SERIAL", "auto")
-# order of the side stream's two table-Adam passes (A/B knob): "wp" window then next-batch
-# prefetch (default), "pw" the prefetch first, "p_w" the prefetch at the fork and the window only
-# once the backward starts (the side stream waits for the forward)
-_SIDE_ORDER = os.environ.get("FBN_SIDE_ORDER", "wp")
-_FIXUP_ON_SIDE = os.environ.get("FBN_FIXUP_ON_SIDE", "auto")
-# one join of the side stream per step after the fold (A/B knob: False joins again before the tail)
-_JOIN_ONCE = True
-# ... or after the gather (fields_fwd then runs with the chip to itself; A/B knob)
-_SIDE_AFTER_GATHER = os.environ.get("FBN_SIDE_AFTER_GATHER", "0") == "1"
-# N > 1: the next batch's routing enqueued after this step's compute (A/B knob)
-_ROUTE_AFTER_COMPUTE = os.environ.get("FBN_ROUTE_AFTER_COMPUTE", "1") == "1"
-# single GPU: the dense gradients' sum of squares inside the table-gradient norm launch (A/B knob)
-_DENSE_SUMSQ_FOLD = os.environ.get("FBN_DENSE_SUMSQ_FOLD", "1") == "1"
+# What the stream-placement A/B rounds settled (measurements: DESIGN §10; their arms are no longer in
+# the code).  bench.py's byte accounting reads these two facts by name: single GPU, the step's bf16
+# weight images are made on the main stream, and with the lazy table Adam their conversion rides in
+# the row claims' launch (fbn_adam_claim_catchup_conv)
+_W16_MODE = "main"
+_HEAD_CONV = True
 # N > 1 (RCCL), opt-in (FBN_EARLY_GRAD_XCHG=1): the gradient-row all-to-all issued right after the
 # fields backward and the dense-gradient all-reduce right after the compute, both asynchronous on
 # the process group's stream beside the remaining work (the loss + table sum of squares then take
@@ -113,18 +75,6 @@ FBN_RING_BF16 = 0x40000000   # include/fibinet.h: ring_n flag, the deferred-grad
 # tests/test_gpu_rccl.py).  Measured no faster at one rank (0.4825 vs 0.4787 ms/step), so
 # the f32 ring stays the default
 _RING_BF16 = os.environ.get("FBN_RING_BF16", "0") == "1"
-# N > 1, the owner's ahead-of-time catch-up of the next step's requested rows in two passes (tagged
-# pre-claims + the four-row replay engine); FBN_OWNER_PF2=0 keeps the one-pass kernel (A/B)
-_OWNER_PF2 = os.environ.get("FBN_OWNER_PF2", "1") != "0"
-# N > 1, the fixed-capacity exchange: the owner's claims and claimed-row catch-up in one launch
-# (fbn_adam_owner_claim_catchup, pre-claims from the owner prefetch); FBN_OWNER_CLAIM_FUSED=0 keeps
-# fbn_owner_claim + fbn_adam_catchup (A/B)
-_OWNER_CLAIM_FUSED = os.environ.get("FBN_OWNER_CLAIM_FUSED", "1") != "0"
-# ... and the widen into the ring slot + the duplicate fold in one pass (fbn_owner_fold; duplicates
-# summed in extra[claimer], applied at the tail); FBN_OWNER_FOLD=0 keeps fbn_ring_slot +
-# fbn_sparse_fixup (A/B)
-_SHARD_W16_SIDE = os.environ.get("FBN_SHARD_W16_SIDE", "1") != "0"
-_OWNER_FOLD = os.environ.get("FBN_OWNER_FOLD", "1") != "0"
 # single GPU, deferred table gradients: the fields backward writes the step's per-sample vectors straight
 # into their deferred-gradient ring slot (fbn_fields_bwd_slot) and every reader takes them there through
 # the pointer cell, so the step tail copies nothing; FBN_GVEC_SLOT=0 keeps the separate gvec buffer and
@@ -172,24 +122,19 @@ def default_lazy_window(d: int) -> int:
     return 128 if d >= 128 else 32
 
 
-def _side_stream(dev):
-    """The side stream; FBN_SIDE_CU_MASK=<hex word>[,<hex word>...] (32 CUs per word, repeated to
-    cover the device) restricts it to a CU subset (hipExtStreamCreateWithCUMask) -- tuning knob
-    (measured: restricting the table-Adam side work to 64 or 32 CUs doubles the step time)."""
-    mask = os.environ.get("FBN_SIDE_CU_MASK")
-    if not mask:
-        return torch.cuda.Stream(device=dev)
-    words = [int(w, 16) for w in mask.split(",")]
-    ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-    n = (ncu + 31) // 32
-    arr = (ctypes.c_uint32 * n)(*[words[i % len(words)] for i in range(n)])
-    hip = ctypes.CDLL("libamdhip64.so")
-    s = ctypes.c_void_p()
-    with torch.cuda.device(dev):
-        rc = hip.hipExtStreamCreateWithCUMask(ctypes.byref(s), n, arr)
-    if rc != 0:
-        raise RuntimeError(f"hipExtStreamCreateWithCUMask failed ({rc})")
-    return torch.cuda.ExternalStream(s.value, device=dev)
+class _Step(NamedTuple):
+    """What one step() call fixes for the launches of its path."""
+    batch: Dict[str, torch.Tensor]
+    labels: torch.Tensor
+    B: int
+    L: int
+    ntot: int                               # the global batch
+    seq: Optional[torch.Tensor]             # batch["item_seq"] (read only where L > 0)
+    main: "torch.cuda.Stream"               # the caller's current stream ...
+    st: int                                 # ... and its handle
+    probe: Optional[Dict[str, list]]
+    masks_out: Optional[Dict[str, torch.Tensor]]
+    next_batch: Optional[Dict[str, torch.Tensor]]
 
 
 class _Segments:
@@ -432,7 +377,7 @@ class FiBiNETTrainer:
         # No collective inside the forward / backward then: the captured compute is ONE segment.
         self.sync_bn = bool(model_cfg.get("sync_bn", True) if sync_bn is None else sync_bn)
         self.bn_coll = self.coll if self.sync_bn else ops.NO_COLLECTIVE
-        self.side = _side_stream(dev)      # eager untouched pass / lazy rolling window / routing ahead
+        self.side = torch.cuda.Stream(device=dev)      # eager untouched pass / lazy rolling window / routing ahead
         self.xchg = RowExchange(rank, world, self.V, d, self.B, max_len, dev, group, stage_on_cpu=stage_on_cpu,
                                 rows_bf16=self.fcfg.bf16, side=self.side, comm=self.native_comm) if sharded else None
         self.stage_on_cpu = stage_on_cpu
@@ -449,8 +394,12 @@ class FiBiNETTrainer:
         if self.table_adam not in ("lazy", "eager", "sparse"):
             raise ValueError(f"table_adam must be 'lazy', 'eager' or 'sparse', not {self.table_adam!r}")
         self.lazy_window = int(lazy_window) if lazy_window is not None else default_lazy_window(d)
-        # single GPU: the side-stream table-Adam passes in sequence on the main stream (see _SIDE_SERIAL)
-        self.side_serial = _SIDE_SERIAL == "1" or (_SIDE_SERIAL == "auto" and d < 128)
+        # the table-Adam side passes (rolling window + next-batch prefetch) in sequence on the main stream
+        # below d = 128, where the side work is small and the cross-queue edges cost more than the overlap
+        # saves (C2, graph-replayed: 0.2833-0.2844 vs 0.2934-0.2952 ms/step; eager 0.30 vs 0.45-0.50, the
+        # host's event waits gone; profiles/r03s2_side_serial_ab.txt); on the side stream from d = 128 on
+        # (C3: the overlap is worth 50 us, 0.4629 vs 0.5128 ms/step) and in step programs (_fork_side)
+        self.side_serial = d < 128
         self.last = self.row_state[:, 2]     # Adam steps applied per table row
         # lazy: deferred table gradients (the step tail's commit) -- pend[r] = the gradient row r
         # received at step last[r], applied at the row's next replay; the last F+1 steps' gradients
@@ -471,7 +420,6 @@ class FiBiNETTrainer:
         # N > 1: forward + backward between the row exchanges replayed as hipGraph segments split at
         # the SyncBN all-reduces (_Segments), after two eager steps; FBN_SHARD_GRAPH=0 keeps it eager
         self.shard_graph = self.sharded and os.environ.get("FBN_SHARD_GRAPH", "1") != "0"
-        self._late_side = None
         self._sg = None
         self._sg_eager = 0
         self._bn_synced_at = -1     # host step of the last rank-0 BatchNorm broadcast (_bn_from_rank0)
@@ -483,7 +431,7 @@ class FiBiNETTrainer:
         self._fc_steps = 0
         self.ring_cell = torch.zeros(2, dtype=torch.int64, device=dev)     # fbn_ring_slot's pointer cell
         self.gvec_slot = _GVEC_SLOT and not sharded and self.deferred       # fbn_fields_bwd_slot (with L > 0)
-        self.norm_in_sums = _NORM_IN_SUMS and _DENSE_SUMSQ_FOLD and not sharded and not self.deterministic
+        self.norm_in_sums = _NORM_IN_SUMS and not sharded and not self.deterministic
         self._gap_checked = False   # norm_in_sums: the unwritten columns of mlp.0.weight's gradient seen zero
         self._fc_grad = None        # fixed-capacity rows, f32, when they are not deferred
         self._fc_extra = None       # fixed-capacity form: duplicates' sums per claimer (zero at rest)
@@ -507,457 +455,206 @@ class FiBiNETTrainer:
         if self.host_step >= self.total_steps:
             raise ValueError(f"Tried to step {self.host_step + 1} times. The specified number of total steps is "
                              f"{self.total_steps}")
-        st = _lib.stream_handle(self.device)
         B = batch["item_id"].shape[0]
         if B > self.B:
             raise ValueError(f"batch of {B} rows exceeds the trainer's batch_size {self.B}")
-        ntot = B * self.world
-        d = self.d
-        cfg = self.fcfg
         seq = batch.get("item_seq")
-        L = cfg.L = seq.shape[1] if seq is not None else 0
+        L = self.fcfg.L = seq.shape[1] if seq is not None else 0
         if L > self.L:
             raise ValueError(f"history length {L} exceeds max_len {self.L}")
-        rows = pos = None
-        main = torch.cuda.current_stream(self.device)
+        # (self.side is not part of the record: callers may swap it between steps, and every edge
+        # below tolerates side == main)
+        s = _Step(batch, labels, B, L, B * self.world, seq, torch.cuda.current_stream(self.device),
+                  _lib.stream_handle(self.device), probe, masks_out, next_batch)
+        gsrc, n_ent, defer_now = self._step_local(s) if self.xchg is None else self._step_sharded(s)
+        self._finish(s, gsrc, n_ent, defer_now)
+        return self.loss
 
+    def _step_local(self, s: _Step):
+        """One GPU: claims (+ catch-up) -> forward -> backward -> duplicate fold -> clip norm, the table-Adam
+        side passes beside them; returns the step tail's gradient source (gsrc, n_ent, defer_now)."""
+        cfg, B, L, d, st, main = self.fcfg, s.B, s.L, self.d, s.st, s.main
+        batch, seq = s.batch, s.seq
         lazy = self.table_adam == "lazy"
-
-        side_hooks = {}
-
-        def catch_up(n_ent, claim=False, before_side=None, on_side=None):
-            # lazy table Adam: the rows claimed this step are brought to `step` Adam steps before
-            # anything reads them; the rolling window (step % F; unclaimed rows, read by nothing
-            # this step) replays on the side stream beside the rest of the step.  claim (single
-            # GPU): the row claims are made inside the same launch (fbn_adam_claim_catchup).
-            # on_side (an event on main at the step's start): the claims run on the side stream,
-            # and the main stream waits for them just before the gather
-            if on_side is not None:
-                _lib.wait_event(self.side, on_side)
-                ev = _events(probe, "adam_catchup", self.side)
-                key = _batch_key(batch["item_id"], seq if L else None)
-                pre = self.preclaim if (self.preclaim is not None and key == self._pre_key) else None
-                self._used_pre = pre is not None
-                self._pre_key = None
-                call("fbn_adam_claim_catchup", ptr(batch["item_id"]), ptr(seq) if L else None, B, L, self.V,
-                     ptr(self.map), ptr(self.slot_row), ptr(self.dup), ptr(self.hasdup), ptr(pre), ptr(self.E),
-                     ptr(self.Em), ptr(self.Ev), self.rows_local, d, self.lazy_window, ptr(self.last),
-                     ptr(self.sched), ptr(self.step_dev), self.wd_g, self.beta2, self.eps, *self._pend_args(),
-                     int(self.decoupled), self.side.cuda_stream)
-                _events_end(ev, self.side)
-                claim_ev = torch.cuda.Event()
-                _lib.record_event(claim_ev, self.side)
-                side_hooks["before_gather"] = lambda: _lib.wait_event(main, claim_ev)
-                side_pass(wait_main=False)
-                return
-            ev = _events(probe, "adam_catchup")
-            if claim:
-                key = _batch_key(batch["item_id"], seq if L else None)
-                pre = self.preclaim if (self.preclaim is not None and key == self._pre_key) else None
-                self._used_pre = pre is not None
-                self._pre_key = None
-                args = (ptr(batch["item_id"]), ptr(seq) if L else None, B, L, self.V, ptr(self.map),
-                        ptr(self.slot_row), ptr(self.dup), ptr(self.hasdup), ptr(pre), ptr(self.E), ptr(self.Em),
-                        ptr(self.Ev), self.rows_local, d, self.lazy_window, ptr(self.last), ptr(self.sched),
-                        ptr(self.step_dev), self.wd_g, self.beta2, self.eps, *self._pend_args(), int(self.decoupled))
-                if head_conv:
-                    # the step head: the bf16 images converted in the same launch as the claims
-                    call("fbn_adam_claim_catchup_conv", *args, *head_conv, st)
-                else:
-                    call("fbn_adam_claim_catchup", *args, st)
-            else:
-                call("fbn_adam_catchup", ptr(self.E), ptr(self.Em), ptr(self.Ev), self.rows_local, d,
-                     ptr(self.slot_row), n_ent, ptr(self.map), self.lazy_window, 1, ptr(self.last), ptr(self.sched),
-                     ptr(self.step_dev), self.wd_g, self.beta2, self.eps, *self._pend_args(), int(self.decoupled), st)
-            _events_end(ev)
-            if before_side is not None:
-                self._w16_ev = start_w16(before_side)   # the side stream: images first, then the window
-            if claim and _SIDE_AFTER_MLP0:
-                side_hooks["after_mlp0"] = side_pass     # forked after the MLP's first GEMM instead
-                return
-            if claim and _SIDE_AFTER_MMPROJ:
-                side_hooks["after_mmproj"] = side_pass   # forked after the step's first GEMM
-                return
-            if claim and _SIDE_AFTER_GATHER:
-                side_hooks["after_fields"] = side_pass   # forked after the gather
-                return
-            side_pass()
-
-        def side_pass(wait_main=True):
-            # a step being recorded as a step program runs its side passes on the side stream at every
-            # d: replayed natively, the two edges cost less than the overlap saves (C2: 0.2071-0.2082
-            # vs 0.2176-0.2190 ms/step, profiles/r04_c2_stream_placement.txt)
-            serial = self.side_serial and not (self._recording and _SIDE_SERIAL == "auto")
-            sst = self.side if not serial else main      # in sequence on main (FBN_SIDE_SERIAL)
-            if wait_main and not serial:
-                _lib.wait_stream(self.side, main)
-
-            def window():
-                ev = _events(probe, "adam_window", sst)
-                call("fbn_adam_catchup", ptr(self.E), ptr(self.Em), ptr(self.Ev), self.rows_local, d, None, 0,
-                     ptr(self.map), self.lazy_window, 2, ptr(self.last), ptr(self.sched), ptr(self.step_dev),
-                     self.wd_g, self.beta2, self.eps, *self._pend_args(), int(self.decoupled), sst.cuda_stream)
-                _events_end(ev, sst)
-
-            order = _SIDE_ORDER if not serial else "wp"
-            if order == "wp":
-                window()
-            prefetch_pass(sst)
-            if order == "pw":
-                window()
-            elif order == "p_w":
-                def late_window():
-                    _lib.wait_stream(self.side, main)      # the forward is done: the window beside the backward
-                    window()
-                self._late_side = late_window
-
-        def prefetch_pass(sst):
-            nb = next_batch
-            if (self.xchg is None and nb is not None and self.prefetch_rows and nb["item_id"].dtype == torch.int64
-                    and nb["item_id"].device == self.device):
-                nseq = nb.get("item_seq")
-                nL = nseq.shape[1] if nseq is not None else 0
-                if nb["item_id"].shape[0] == B and nL == L:   # claims made now are valid for that step
-                    self._pre_key = _batch_key(nb["item_id"], nseq if nL else None)
-                elif d < 128:
-                    return                                    # the one-pass form needs wave-wide rows
-                ev = _events(probe, "adam_prefetch", sst)
-                nB = nb["item_id"].shape[0]
-                if (_PF_BINNED and self._pre_key is not None and self.pf_ws is not None
-                        and nB * (nL + 1) <= self.B * (self.L + 1)):
-                    call("fbn_adam_prefetch_binned", ptr(nb["item_id"]), ptr(nseq) if nL else None, nB, nL,
-                         self.V, ptr(self.map), ptr(self.preclaim), ptr(self.E), ptr(self.Em), ptr(self.Ev), d,
-                         ptr(self.last), ptr(self.sched), ptr(self.step_dev), self.wd_g, self.beta2, self.eps,
-                         *self._pend_args(), int(self.decoupled), ptr(self.pf_ws), self.pf_ws.numel(),
-                         sst.cuda_stream)
-                    _events_end(ev, sst)
-                    return
-                call("fbn_adam_prefetch", ptr(nb["item_id"]), ptr(nseq) if nL else None, nB, nL,
-                     self.V, ptr(self.map), ptr(self.preclaim if self._pre_key is not None else None), ptr(self.E),
-                     ptr(self.Em), ptr(self.Ev), d, ptr(self.last),
-                     ptr(self.sched), ptr(self.step_dev), self.wd_g, self.beta2, self.eps, *self._pend_args(),
-                     int(self.decoupled), sst.cuda_stream)
-                _events_end(ev, sst)
-
-        def start_untouched_adam():
-            # eager mode: every row this shard's batch does not touch gets g = wd * p, independent
-            # of the backward -> concurrently on the side stream
-            _lib.wait_stream(self.side, main)
-            ev = _events(probe, "adam_table", self.side)
-            call("fbn_adam_table", ptr(self.E), ptr(self.Em), ptr(self.Ev), self.rows_local, d, ptr(self.map),
-                 None, None, None, 1, None, ptr(self.sched), ptr(self.step_dev), self.wd_g, self.beta2, self.eps, 1,
-                 self.side.cuda_stream)
-            _events_end(ev, self.side)
-
-        w16_ev = None
-
-        def start_w16(after=None):
-            # bf16 weight images (they depend only on the weights the previous step wrote) on the side
-            # stream, beside the row claims and the claimed-row catch-up
-            if after is None:
-                _lib.wait_stream(self.side, main)
-            else:
-                _lib.wait_event(self.side, after)
-            with torch.cuda.stream(self.side):
-                self.acts["w16"] = ops.bf16_weights(self.p, d, self.acts, self.side.cuda_stream,
-                                                    x=batch["item_emb_d128"])
-            ev = torch.cuda.Event()
-            _lib.record_event(ev, self.side)
-            return ev
-
-        # bf16_fwd training on the split-bf16 x3 backward: the forward's weight images (and their lo
-        # images) made here too, in the claims' launch, instead of at the forward's start
+        # the step's bf16 weight images, made on the main stream (a cross-queue wait inside a replayed
+        # graph costs ~10 us, about what the conversion itself takes).  bf16_fwd training on the split-bf16
+        # x3 backward: the forward's weight images (and their lo images) made here too
         w16_img = bool(cfg.fwd16 and not cfg.bf16 and ops._SPLIT3 and not cfg.bilinear_each and cfg.training)
-        w16_main = (cfg.bf16 or w16_img) and self.xchg is None and _W16_MODE == "main"
-        self.acts["w16_images"] = w16_main and w16_img
-        w16_late = cfg.bf16 and self.xchg is None and lazy and _W16_MODE == "late"
-        claim_side = None
-        if (self.xchg is None and lazy and _CLAIM_ON_SIDE and not w16_late and not _SIDE_AFTER_MLP0
-                and not _SIDE_AFTER_MMPROJ and not _SIDE_AFTER_GATHER):
-            claim_side = torch.cuda.Event()          # the step's start: the claims wait for nothing later
-            _lib.record_event(claim_side, main)
-        head_conv = None
-        if w16_main and self.xchg is None and lazy and claim_side is None and _HEAD_CONV:
-            # on the main stream, in the claims' launch (fbn_adam_claim_catchup_conv): the two are
-            # independent, so they run side by side instead of one launch after the other
-            jobs, njobs, self.acts["w16"] = ops.bf16_weight_jobs(self.p, d, self.acts, x=batch["item_emb_d128"],
-                                                                 images=w16_img)
-            head_conv = (ctypes.cast(jobs, ctypes.c_void_p).value, njobs)
-        elif w16_main:
-            # on the main stream ahead of the claims: a cross-queue wait inside a replayed graph
-            # costs ~10 us, about what the conversion itself takes
-            self.acts["w16"] = ops.bf16_weights(self.p, d, self.acts, st, x=batch["item_emb_d128"], images=w16_img)
-        elif cfg.bf16 and not w16_late and (self.xchg is None or _SHARD_W16_SIDE):
-            # (N > 1: beside the row exchange)
-            w16_ev = start_w16()
-        if self.xchg is not None:
-            sparse = {"map": self.map, "slot_row": self.slot_row}
-            if lazy and _OWNER_CLAIM_FUSED:
-                def owner_claim_catchup(ids, n):
-                    # fixed-capacity form: claims + claimed-row catch-up in one launch, the claims
-                    # decided by the pre-claim tags the previous step's owner prefetch posted for
-                    # this very routing (those with a tag of this step; the rest by CAS)
-                    ev = _events(probe, "adam_catchup")
-                    pre = self.row_state.view(torch.int64)[:, 0] if (self.prefetch_owner and _OWNER_PF2) else None
-                    call("fbn_adam_owner_claim_catchup", ptr(ids), n, int(self.rank == 0), ptr(self.map),
-                         ptr(self.slot_row), ptr(pre), ptr(self.E), ptr(self.Em), ptr(self.Ev), self.rows_local, d,
-                         self.lazy_window, ptr(self.last), ptr(self.sched), ptr(self.step_dev), self.wd_g,
-                         self.beta2, self.eps, *self._pend_args(), int(self.decoupled), st)
-                    _events_end(ev)
-                    side_pass()
-                sparse["claim_catchup"] = owner_claim_catchup
-            rows = self.xchg.forward(batch["item_id"], seq, self.E, sparse, self.err,
-                                     before_gather=catch_up if lazy else None)
-            pos = self.xchg.cur_pos
-            fwd_ev = torch.cuda.Event()
-            _lib.record_event(fwd_ev, main)
-        route_ahead = None
-        if self.xchg is not None and next_batch is not None:
-            def route_ahead():
-                own = self.prefetch_owner and lazy
-                self.xchg.prepare(next_batch["item_id"], next_batch.get("item_seq"), self.err, send_rows=own,
-                                  after=fwd_ev)
-                if own and self.xchg.next_lids is not None:
-                    # after this step's claims and window (self.side), once the requests arrived
-                    _lib.wait_stream(self.side, self.xchg.side)
-                    ev = _events(probe, "adam_prefetch", self.side)
-                    call("fbn_adam_prefetch_rows", ptr(self.xchg.next_lids), self.xchg.next_lids.numel(),
-                         int(self.rank == 0), self.rows_local, ptr(self.map),
-                         ptr(self.row_state.view(torch.int64)[:, 0]) if _OWNER_PF2 else None, ptr(self.E), ptr(self.Em),
-                         ptr(self.Ev), d, ptr(self.last), ptr(self.sched), ptr(self.step_dev), self.wd_g, self.beta2,
-                         self.eps, *self._pend_args(), int(self.decoupled), self.side.cuda_stream)
-                    _events_end(ev, self.side)
-                    self.xchg.next_lids.record_stream(self.side)
-            if not _ROUTE_AFTER_COMPUTE:
-                route_ahead()
-                route_ahead = None
-        elif self.xchg is None and lazy:
-            if w16_late:
-                # captured after the claimed-row catch-up's launch, so a graph replay starts the
-                # catch-up first; the images follow on the side stream, still beside it (they wait
-                # only for what preceded the catch-up)
-                step_start = torch.cuda.Event()
-                _lib.record_event(step_start, main)
-                catch_up(B * (L + 1), claim=True, before_side=step_start)
-                w16_ev = self._w16_ev
-            else:
-                catch_up(B * (L + 1), claim=True, on_side=claim_side)
-        elif self.xchg is None:
+        w16 = bool(cfg.bf16 or w16_img)
+        self.acts["w16_images"] = w16_img
+        if lazy:
+            head_conv = None
+            if w16:
+                # in the claims' launch (fbn_adam_claim_catchup_conv): the two are independent, so they
+                # run side by side instead of one launch after the other
+                jobs, njobs, self.acts["w16"] = ops.bf16_weight_jobs(self.p, d, self.acts, x=batch["item_emb_d128"],
+                                                                     images=w16_img)
+                head_conv = (ctypes.cast(jobs, ctypes.c_void_p).value, njobs)
+            self._claim_catchup(s, head_conv)
+            self._side_passes(s)
+        else:
+            if w16:
+                # a launch of their own: there is no claims launch to ride in
+                self.acts["w16"] = ops.bf16_weights(self.p, d, self.acts, st, x=batch["item_emb_d128"],
+                                                    images=w16_img)
             call("fbn_claim_rows", ptr(batch["item_id"]), ptr(seq) if L else None, B, L, self.V, ptr(self.map),
                  ptr(self.slot_row), ptr(self.dup), ptr(self.hasdup), st)
-        if w16_ev is not None:
-            _lib.wait_event(main, w16_ev)
-        graphed = False
-        # (not inside a graph capture: there each cross-queue edge costs ~10 us of the replay)
-        fixup_side = (self.xchg is None and (_FIXUP_ON_SIDE == "1" or (_FIXUP_ON_SIDE == "auto" and not self.side_serial
-                                                                        and not torch.cuda.is_current_stream_capturing()))
-                      and not self.deterministic and L > 0
-                      and not self._early_grad_xchg())
+        # the duplicate fold on the side stream whenever the side stream is in use (not inside a graph
+        # capture: there each cross-queue edge costs ~10 us of the replay)
+        fixup_side = (not self.side_serial and not torch.cuda.is_current_stream_capturing()
+                      and not self.deterministic and L > 0)
         # the step's per-sample vectors: gvec, or (gvec_slot) ring slot step % ring_n, which the fields
         # backward chooses on the device -- its readers then go through the pointer cell
-        slot = self.gvec_slot and self.xchg is None and L > 0
+        slot = self.gvec_slot and L > 0
         gv, gcell = (self.ring_cell, FBN_GRAD_CELL) if slot else (self.gvec, 0)
-        in_sums = self.norm_in_sums and self.xchg is None and L > 0
-
-        def table_norm(stream):
-            # (in_sums) the table part of the clip norm, right after the fold, on the fold's stream
-            call("fbn_sumsq_sparse_norms", ptr(self.gnorm), ptr(gv), ptr(self.extra), ptr(self.slot_row),
-                 (L + 1) | gcell, B * (L + 1), d, ptr(self.sumsq), None, None, 0, stream)
-        if (self.xchg is not None and self.shard_graph and probe is None and masks_out is None
-                and self.table_adam != "eager" and not self._recording):
-            sendbuf = self.xchg.make_sendbuf()
-            graphed = self._sharded_compute(batch, labels, pos, cfg, ntot, B, L)
-        if not graphed:
-            a = ops.forward(self.p, batch, cfg, self.rng, table_rows=rows, pos=pos, err=self.err, labels=labels,
-                            w16_ready=w16_ev is not None or w16_main,
-                            loss_denom=float(ntot), coll=self.bn_coll, ntot=self._bn_n(ntot, B), acts=self.acts,
-                            masks_out=masks_out,
-                            probe=probe, count_batches=False,     # num_batches_tracked: fbn_step_end
-                            after_gather=start_untouched_adam if self.table_adam == "eager" else None,
-                            hooks=side_hooks)
-            if self._late_side is not None:
-                self._late_side()
-                self._late_side = None
-            sendbuf = self.xchg.make_sendbuf() if self.xchg is not None else None
-            bhooks = {"after_fields_bwd": self._grad_xchg_start} if self._early_grad_xchg() else None
-            if fixup_side:
-                def fork_fixup():
+        in_sums = self.norm_in_sums and L > 0
+        n_ent = B * (L + 1)               # entry e = b*(L+1)+t; duplicates -> extra[claimer]
+        bhooks = None
+        if fixup_side:
+            def fork_fold():
+                _lib.wait_stream(self.side, main)
+                self._fold_duplicates(s, gv, (L + 1) | gcell, in_sums, self.side.cuda_stream)
+            bhooks = {"after_fields_bwd": fork_fold}
+            if _WGRAD_EARLY and cfg.bf16:
+                def early_wgrad(sums):
                     _lib.wait_stream(self.side, main)
-                    call("fbn_sparse_fixup_dup", ptr(self.dup), B * (L + 1), ptr(gv), ptr(self.extra),
-                         ptr(self.slot_row), (L + 1) | gcell, d, self.side.cuda_stream)
-                    if in_sums:
-                        table_norm(self.side.cuda_stream)
-                bhooks = {"after_fields_bwd": fork_fixup}
-                if _WGRAD_EARLY and cfg.bf16:
-                    def early_wgrad(sums):
-                        _lib.wait_stream(self.side, main)
-                        sums.launch_group(self.side.cuda_stream, probe, tstream=self.side)
-                    bhooks["after_bilinear_bwd"] = early_wgrad
-                    bhooks["before_flush"] = lambda: _lib.wait_stream(main, self.side)
-            gaps = ops.backward(self.p, batch, a, a["gout"], self.g, cfg,
-                         dense_sumsq=self.sumsq if in_sums else None,
-                         gvec=self.gvec if self.xchg is None and not slot else None,
-                         gslot=(self.ring, self.ring_n, self._ring_stride(), self.step_dev, self.ring_cell)
-                         if slot else None,
-                         gnorm=self.gnorm if self.xchg is None else None,
-                         pos=pos, sendbuf=sendbuf, coll=self.bn_coll, ntot=self._bn_n(ntot, B),
-                         extra_sums=[(a["loss_terms"], B, 1, self.loss, 1.0 / ntot)], probe=probe,
-                         hooks=bhooks)
-            if gaps and not self._gap_checked and not torch.cuda.is_current_stream_capturing():
-                for key, ncols, remap in gaps:      # once: a synchronising check
-                    ops.check_unwritten_columns_zero(self.g[key], ncols, remap)
-                self._gap_checked = True
+                    sums.launch_group(self.side.cuda_stream, s.probe, tstream=self.side)
+                bhooks["after_bilinear_bwd"] = early_wgrad
+                bhooks["before_flush"] = lambda: _lib.wait_stream(main, self.side)
+        self._forward_backward(s, w16_ready=w16, hooks=bhooks,
+                               after_gather=(lambda: self._untouched_adam(s)) if self.table_adam == "eager"
+                               else None,
+                               dense_sumsq=self.sumsq if in_sums else None, gvec=None if slot else self.gvec,
+                               gslot=(self.ring, self.ring_n, self._ring_stride(), self.step_dev, self.ring_cell)
+                               if slot else None, gnorm=self.gnorm)
+        joined = False
+        if self.deterministic:
+            if L == 0:
+                raise ValueError("deterministic mode needs the item_seq history (L > 0)")
+            # extra[claimer] becomes the FULL row gradient (Lp1 | FBN_GRAD_FULL for the readers)
+            gsrc = (gv, self.extra, (L + 1) | FBN_GRAD_FULL | gcell)
+            call("fbn_sparse_fold_fx", ptr(self.dup), ptr(self.hasdup), n_ent, ptr(gv), ptr(self.slot_row),
+                 gsrc[2], d, ptr(self.fx), st)
+        else:
+            gsrc = (gv, self.extra, (L + 1) | gcell)
+            if fixup_side:
+                _lib.wait_stream(main, self.side)     # the fold (and the side's table passes) done
+                joined = True
+            else:
+                self._fold_duplicates(s, gv, gsrc[2], in_sums, st)
+        if not in_sums:
+            self._clip_norm_local(s, gsrc, n_ent)
+        if not joined:
+            # side-stream table pass done before map entries are reset (already joined after the fold:
+            # nothing went to the side stream since, and each join costs ~6 us of main-stream idle)
+            _lib.wait_stream(main, self.side)
+        return gsrc, n_ent, self.deferred
+
+    def _step_sharded(self, s: _Step):
+        """Row-sharded: row exchange (the owner's claims + catch-up inside it) -> compute -> gradient-row
+        exchange -> owner fold -> clip norm over the ranks, the next batch routed ahead beside them;
+        returns the step tail's gradient source (gsrc, n_ent, defer_now)."""
+        cfg, x, main = self.fcfg, self.xchg, s.main
+        batch = s.batch
+        lazy = self.table_adam == "lazy"
+        self.acts["w16_images"] = False
+        w16_ev = self._w16_on_side(s) if cfg.bf16 else None      # beside the row exchange
+        sparse = {"map": self.map, "slot_row": self.slot_row}
+        if lazy:
+            sparse["claim_catchup"] = lambda ids, n: self._owner_claim_catchup(s, ids, n)
+        # (before_gather: the host-split form's catch-up -- calibration and overflow steps)
+        rows = x.forward(batch["item_id"], s.seq, self.E, sparse, self.err,
+                         before_gather=(lambda n: self._owner_catchup(s, n)) if lazy else None)
+        pos = x.cur_pos
+        fwd_ev = torch.cuda.Event()
+        _lib.record_event(fwd_ev, main)
+        if w16_ev is not None:
+            _lib.wait_event(main, w16_ev)
+        sendbuf = x.make_sendbuf()
+        graphed = False
+        if (self.shard_graph and s.probe is None and s.masks_out is None and self.table_adam != "eager"
+                and not self._recording):
+            graphed = self._sharded_compute(batch, s.labels, pos, cfg, s.ntot, s.B, s.L)
+        if not graphed:
+            self._forward_backward(s, w16_ready=w16_ev is not None, rows=rows, pos=pos, sendbuf=sendbuf,
+                                   after_gather=(lambda: self._untouched_adam(s)) if self.table_adam == "eager"
+                                   else None,
+                                   hooks={"after_fields_bwd": self._grad_xchg_start} if self._early_grad_xchg()
+                                   else None)
         dense_work = None
-        if self.sharded and self._early_grad_xchg() and self.native_comm is None and not self.coll.det:
+        if self._early_grad_xchg() and self.native_comm is None and not self.coll.det:
             # the dense gradients are final once the compute is: their all-reduce goes out now,
             # asynchronously behind the gradient-row all-to-all on the process group's stream,
             # beside the owner's widen / fold / norm; only the loss and the table-gradient sum of
             # squares (known after those) travel at the end
             dense_work = dist.all_reduce(self.flat_g, group=self.coll.group, async_op=True)
-        if route_ahead is not None:
+        if s.next_batch is not None:
             # the host enqueues the next batch's routing (and the owner-side prefetch) only after
             # this step's compute: on the GPU it still starts right after this step's row exchange
             # (it waits on fwd_ev only), but the compute no longer waits for the host to get
             # through ~10 side-stream launches and a collective first
-            route_ahead()
-        joined = False
-        fold_done = False
-        if self.xchg is None:
-            # single GPU: per-sample vectors; entry e = b*(L+1)+t; duplicates -> extra[claimer]
-            n_ent = B * (L + 1)
-            if self.deterministic:
-                if L == 0:
-                    raise ValueError("deterministic mode needs the item_seq history (L > 0)")
-                # extra[claimer] becomes the FULL row gradient (Lp1 | FBN_GRAD_FULL for the readers)
-                gsrc = (gv, self.extra, (L + 1) | FBN_GRAD_FULL | gcell)
-                call("fbn_sparse_fold_fx", ptr(self.dup), ptr(self.hasdup), n_ent, ptr(gv), ptr(self.slot_row),
-                     gsrc[2], d, ptr(self.fx), st)
-            else:
-                gsrc = (gv, self.extra, (L + 1) | gcell)
-                if fixup_side:
-                    _lib.wait_stream(main, self.side)     # the fold (and the side's table passes) done
-                    joined = True
-                else:
-                    call("fbn_sparse_fixup_dup", ptr(self.dup), n_ent, ptr(gv), ptr(self.extra),
-                         ptr(self.slot_row), gsrc[2], d, st)
-                    if in_sums:
-                        table_norm(st)
-        else:
-            # owner: one received row per entry -- straight into this step's deferred-gradient ring
-            # slot when it fits, else a buffer of its own and the rows applied at the step end
-            x = self.xchg
-            n_ent = x.n_recv
-            fold_done = False
-            if x.fc_active:
-                # fixed-capacity form: the rows arrive in the fixed wire buffer; deferred, they move
-                # into ring slot step % ring_n chosen on the device (a replayed step program gets the
-                # right slot), and the readers take them through the slot's pointer cell
-                wire = x.backward_finish() if x._pending is not None else x.backward(sendbuf)
-                defer_now = self.deferred and n_ent <= self.ring_cap
-                # (this rank's own block was not sent: its rows are read from the send buffer itself)
-                lo, cnt = x.fc_self_rows
-                if self._fc_extra is None or self._fc_extra.shape[0] < n_ent:
-                    self._fc_extra = _lib.persistent(
-                        lambda: torch.zeros((n_ent, d), dtype=torch.float32, device=self.device))
-                if defer_now:
-                    ring, ring_n, stride = self.ring, self._ring_n_arg(), self._ring_stride()
-                else:
-                    if self._fc_grad is None or self._fc_grad.shape[0] < n_ent:
-                        self._fc_grad = _lib.persistent(
-                            lambda: torch.empty((n_ent, d), dtype=torch.float32, device=self.device))
-                    ring, ring_n, stride = self._fc_grad, 1, n_ent * d
-                rb = FBN_GRAD_BF16 if (defer_now and self.ring_bf16) else 0
-                if _OWNER_FOLD or self.deterministic or rb:
-                    # the widen into the ring slot and the duplicate fold in one pass: a claimer's row is
-                    # stored, a duplicate's added into extra[claimer] (flagged; applied at the tail); the
-                    # claimers' squares summed on the way (the flagged ones corrected below).  Deterministic:
-                    # the duplicates go to the fixed-point accumulator, extra becomes the FULL row gradient
-                    fx = self._fold_bufs(n_ent)
-                    call("fbn_owner_fold", ptr(x.recv_ids), n_ent, self.rank, ptr(self.map), ptr(self.slot_row),
-                         ptr(wire), int(wire.dtype == torch.bfloat16), ptr(x.fc_send) if cnt else None, lo, cnt,
-                         ptr(ring), ring_n, stride, ptr(self.step_dev), ptr(self.ring_cell), ptr(self._fc_extra), d,
-                         ptr(self._fc_part), ptr(fx), st)
-                    gsrc = (self.ring_cell, self._fc_extra,
-                            1 | FBN_GRAD_CELL | rb | (FBN_GRAD_FULL if fx is not None else 0))
-                    fold_done = True
-                else:
-                    call("fbn_ring_slot", ptr(ring), ring_n, stride, ptr(self.step_dev), ptr(self.ring_cell),
-                         ptr(wire), int(wire.dtype == torch.bfloat16), n_ent * d, ptr(x.fc_send) if cnt else None,
-                         lo * d, cnt * d, st)
-                    gsrc = (self.ring_cell, None, 1 | FBN_GRAD_CELL)
-            else:
-                slot = self._grad_slot()
-                defer_now = slot is not None
-                if x._pending is not None:          # issued right after the fields backward
-                    grows = x.backward_finish()
-                else:
-                    grows = x.backward(sendbuf, out=slot)
-                gsrc = (grows, None, 1)
-                g16 = grows.dtype == torch.bfloat16          # received straight into a bf16 ring slot
-                if (self.deterministic or g16) and n_ent > 0:
-                    # the host-split form (calibration steps, overflow fallbacks): the owner fold in
-                    # place over the received rows (the claimer's row is rewritten with itself; ring_n
-                    # 1, the cell -> grows) -- deterministic (fixed point), or a bf16 ring slot (no
-                    # float atomics into bf16 rows: the duplicates go to extra)
-                    fx = self._fold_bufs(n_ent)
-                    call("fbn_owner_fold", ptr(x.recv_ids), n_ent, self.rank, ptr(self.map), ptr(self.slot_row),
-                         ptr(grows), int(g16), None, 0, 0, ptr(grows), 1 | (FBN_RING_BF16 if g16 else 0), n_ent * d,
-                         ptr(self.step_dev), ptr(self.ring_cell), ptr(self._fc_extra), d, ptr(self._fc_part), ptr(fx),
-                         st)
-                    gsrc = (self.ring_cell, self._fc_extra, 1 | FBN_GRAD_CELL | (FBN_GRAD_BF16 if g16 else 0) |
-                            (FBN_GRAD_FULL if fx is not None else 0))
-                    fold_done = True
-            if not fold_done:
-                call("fbn_sparse_fixup", None, None, ptr(x.recv_ids), n_ent, 0, self.V, self.rank, ptr(self.map),
-                     ptr(gsrc[0]), None, ptr(self.slot_row), gsrc[2], d, st)
-        # clip_grad_norm_(10): dense grads (identical on every rank) + disjoint table shards
-        tab_acc = self.sumsq_tab if self.sharded else self.sumsq
-        dense_done = False
-        if in_sums:
-            dense_done = True      # both parts are in the slots (or on their way: the side stream is joined)
-        elif self.xchg is None and L > 0:
-            # one process: the dense gradients are final here, so their squares ride along
-            fold = not self.sharded and _DENSE_SUMSQ_FOLD
-            call("fbn_sumsq_sparse_norms", ptr(self.gnorm), ptr(gsrc[0]), ptr(gsrc[1]), ptr(self.slot_row), gsrc[2],
-                 n_ent, d, ptr(tab_acc), ptr(self.fx), ptr(self.flat_g) if fold else None,
-                 self.n_dense if fold else 0, st)
-            dense_done = fold
-        elif fold_done:
-            # the fold summed the claimers' own rows; only the flagged ones (duplicates) remain
-            call("fbn_sumsq_flagged", ptr(self.slot_row), n_ent, ptr(self.ring_cell), ptr(self._fc_extra), d,
-                 ptr(self._fc_part), ptr(tab_acc), ptr(self._fx_sh) if self.deterministic else None,
-                 int(bool(gsrc[2] & FBN_GRAD_BF16)), st)
-        else:
-            call("fbn_sumsq_sparse", ptr(gsrc[0]), ptr(gsrc[1]), ptr(self.slot_row), gsrc[2], n_ent, d, ptr(tab_acc),
-                 st)
-        if self.sharded:
-            # ONE all-reduce: dense grads + the loss + this shard's table-gradient sumsq
-            o = self.n_dense
-            call("fbn_pack_extras", ptr(self.loss), ptr(self.sumsq_tab), ptr(self.flat_g_ext[o:]), st)
-            if dense_work is not None:
-                dist.all_reduce(self.flat_g_ext[o:o + 2], group=self.coll.group)
-                dense_work.wait()
-            else:
-                self.coll.allreduce_(self.flat_g_ext[:o + 2])
-            if not dense_done:
-                # the unpack and the dense gradients' squares in one launch
-                call("fbn_unpack_sumsq", ptr(self.flat_g_ext[o:]), ptr(self.loss), ptr(self.flat_g), self.n_dense,
-                     ptr(self.sumsq), st)
-                dense_done = True
-            else:
-                call("fbn_unpack_extras", ptr(self.flat_g_ext[o:]), ptr(self.loss), ptr(self.sumsq), st)
-        if not dense_done:
-            call("fbn_sumsq", ptr(self.flat_g), self.n_dense, None, 0, ptr(self.sumsq), st)
-        if not (joined and _JOIN_ONCE):
-            # side-stream table pass done before map entries are reset (already joined after the
-            # fold: nothing went to the side stream since, and each join costs ~6 us of main-stream idle)
-            _lib.wait_stream(main, self.side)
-        if self.xchg is None:
-            defer_now = self.deferred
+            self._route_ahead(s, fwd_ev)
+        gsrc, n_ent, defer_now, fold_done = self._owner_fold(s, sendbuf)
+        self._clip_norm_sharded(s, gsrc, n_ent, fold_done, dense_work)
+        # side-stream table pass done before map entries are reset
+        _lib.wait_stream(main, self.side)
+        return gsrc, n_ent, defer_now
+
+    # ---- launches of both paths
+    def _forward_backward(self, s: _Step, w16_ready: bool, hooks=None, after_gather=None, rows=None, pos=None,
+                          **grads) -> None:
+        """The eager forward + backward; grads: where ops.backward puts the table gradient (one GPU:
+        gvec / gslot, gnorm, dense_sumsq; sharded: sendbuf)."""
+        cfg, B, ntot = self.fcfg, s.B, s.ntot
+        a = ops.forward(self.p, s.batch, cfg, self.rng, table_rows=rows, pos=pos, err=self.err, labels=s.labels,
+                        w16_ready=w16_ready, loss_denom=float(ntot), coll=self.bn_coll, ntot=self._bn_n(ntot, B),
+                        acts=self.acts, masks_out=s.masks_out,
+                        probe=s.probe, count_batches=False,     # num_batches_tracked: fbn_step_end
+                        after_gather=after_gather)
+        gaps = ops.backward(self.p, s.batch, a, a["gout"], self.g, cfg, pos=pos, coll=self.bn_coll,
+                            ntot=self._bn_n(ntot, B),
+                            extra_sums=[(a["loss_terms"], B, 1, self.loss, 1.0 / ntot)], probe=s.probe,
+                            hooks=hooks, **grads)
+        if gaps and not self._gap_checked and not torch.cuda.is_current_stream_capturing():
+            for key, ncols, remap in gaps:      # once: a synchronising check
+                ops.check_unwritten_columns_zero(self.g[key], ncols, remap)
+            self._gap_checked = True
+
+    def _fork_side(self, s: _Step):
+        """The stream of this step's table-Adam side passes: the side stream, forked off main here -- or
+        main itself (side_serial), the passes in sequence.  A step being recorded as a step program runs
+        them on the side stream at every d: replayed natively, the two edges cost less than the overlap
+        saves (C2: 0.2071-0.2082 vs 0.2176-0.2190 ms/step, profiles/r04_c2_stream_placement.txt)."""
+        if self.side_serial and not self._recording:
+            return s.main
+        _lib.wait_stream(self.side, s.main)
+        return self.side
+
+    def _window(self, s: _Step, sst) -> None:
+        """Lazy table Adam: the rolling window (step % F; unclaimed rows, read by nothing this step)."""
+        ev = _events(s.probe, "adam_window", sst)
+        call("fbn_adam_catchup", ptr(self.E), ptr(self.Em), ptr(self.Ev), self.rows_local, self.d, None, 0,
+             ptr(self.map), self.lazy_window, 2, *self._replay_args(), sst.cuda_stream)
+        _events_end(ev, sst)
+
+    def _untouched_adam(self, s: _Step) -> None:
+        """Eager table Adam: every row this shard's batch does not touch gets g = wd * p, independent
+        of the backward -> concurrently on the side stream (forked after the gather)."""
+        _lib.wait_stream(self.side, s.main)
+        ev = _events(s.probe, "adam_table", self.side)
+        call("fbn_adam_table", ptr(self.E), ptr(self.Em), ptr(self.Ev), self.rows_local, self.d, ptr(self.map),
+             None, None, None, 1, None, ptr(self.sched), ptr(self.step_dev), self.wd_g, self.beta2, self.eps, 1,
+             self.side.cuda_stream)
+        _events_end(ev, self.side)
+
+    def _finish(self, s: _Step, gsrc, n_ent: int, defer_now: bool) -> None:
+        """The step tail: dense Adam with the clip, the table step over gsrc's n_ent entries, the claims'
+        reset and the step end -- then the heartbeat, the exchange's calibration and the host step count."""
+        d, st = self.d, s.st
         if defer_now:
             # ONE launch: dense Adam with clip_grad_norm_(10), the table step (deferred to each row's
             # next replay; rows with duplicates now), map/slot_row reset, step end
-            ev = _events(probe, "adam_tail")
+            ev = _events(s.probe, "adam_tail")
             call("fbn_adam_step_tail", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v),
                  self.n_dense, ptr(self.sumsq), self.max_norm, ptr(self.coef), ptr(self.norm), ptr(self.E),
                  ptr(self.Em), ptr(self.Ev), d, ptr(self.map), ptr(gsrc[0]), ptr(gsrc[1]), ptr(self.slot_row), gsrc[2],
@@ -972,10 +669,11 @@ class FiBiNETTrainer:
             call("fbn_adam_dense", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v),
                  self.n_dense, None, ptr(self.sched), ptr(self.step_dev), self.wd_g, self.beta2, self.eps,
                  ptr(self.sumsq), self.max_norm, ptr(self.coef), ptr(self.norm), st)
-            ev = _events(probe, "adam_touched")
+            ev = _events(s.probe, "adam_touched")
             call("fbn_adam_touched", ptr(self.E), ptr(self.Em), ptr(self.Ev), d, ptr(self.map), ptr(gsrc[0]),
                  ptr(gsrc[1]), ptr(self.slot_row), gsrc[2], n_ent, ptr(self.coef), ptr(self.sched),
-                 ptr(self.step_dev), self.wd_g, self.beta2, self.eps, ptr(self.last) if lazy else None, st)
+                 ptr(self.step_dev), self.wd_g, self.beta2, self.eps,
+                 ptr(self.last) if self.table_adam == "lazy" else None, st)
             _events_end(ev)
             self.slot_row[:n_ent].fill_(-1)
             call("fbn_step_end", ptr(self.step_dev), ptr(self.rng), ptr(self.sumsq),
@@ -988,7 +686,210 @@ class FiBiNETTrainer:
         if self.fc_wanted and not self.xchg.cap and not self.xchg.fc_active:
             self._fc_calibrate()
         self.host_step += 1
-        return self.loss
+
+    # ---- launches of the one-GPU step
+    def _claim_catchup(self, s: _Step, head_conv) -> None:
+        """Lazy table Adam: the row claims and, in the same launch, the claimed rows brought to `step`
+        Adam steps before anything reads them (head_conv: and the step's bf16 images converted).  The
+        claims are the pre-claims the previous step's prefetch posted, if it posted them for this batch."""
+        batch, seq, L = s.batch, s.seq, s.L
+        ev = _events(s.probe, "adam_catchup")
+        key = _batch_key(batch["item_id"], seq if L else None)
+        pre = self.preclaim if (self.preclaim is not None and key == self._pre_key) else None
+        self._used_pre = pre is not None
+        self._pre_key = None
+        args = (ptr(batch["item_id"]), ptr(seq) if L else None, s.B, L, self.V, ptr(self.map),
+                ptr(self.slot_row), ptr(self.dup), ptr(self.hasdup), ptr(pre), ptr(self.E), ptr(self.Em),
+                ptr(self.Ev), self.rows_local, self.d, self.lazy_window, *self._replay_args())
+        if head_conv:
+            call("fbn_adam_claim_catchup_conv", *args, *head_conv, s.st)
+        else:
+            call("fbn_adam_claim_catchup", *args, s.st)
+        _events_end(ev)
+
+    def _side_passes(self, s: _Step) -> None:
+        """The rolling window, then the next batch's prefetch, beside the rest of the step."""
+        sst = self._fork_side(s)
+        self._window(s, sst)
+        self._prefetch_next(s, sst)
+
+    def _prefetch_next(self, s: _Step, sst) -> None:
+        """The next batch's rows that this batch does not touch brought up to date now, and (a next
+        batch of this batch's shape) its row claims decided ahead."""
+        nb, B, L, d = s.next_batch, s.B, s.L, self.d
+        if not (nb is not None and self.prefetch_rows and nb["item_id"].dtype == torch.int64
+                and nb["item_id"].device == self.device):
+            return
+        nseq = nb.get("item_seq")
+        nL = nseq.shape[1] if nseq is not None else 0
+        if nb["item_id"].shape[0] == B and nL == L:   # claims made now are valid for that step
+            self._pre_key = _batch_key(nb["item_id"], nseq if nL else None)
+        elif d < 128:
+            return                                    # the one-pass form needs wave-wide rows
+        ev = _events(s.probe, "adam_prefetch", sst)
+        nB = nb["item_id"].shape[0]
+        if (_PF_BINNED and self._pre_key is not None and self.pf_ws is not None
+                and nB * (nL + 1) <= self.B * (self.L + 1)):
+            call("fbn_adam_prefetch_binned", ptr(nb["item_id"]), ptr(nseq) if nL else None, nB, nL,
+                 self.V, ptr(self.map), ptr(self.preclaim), ptr(self.E), ptr(self.Em), ptr(self.Ev), d,
+                 *self._replay_args(), ptr(self.pf_ws), self.pf_ws.numel(), sst.cuda_stream)
+        else:
+            call("fbn_adam_prefetch", ptr(nb["item_id"]), ptr(nseq) if nL else None, nB, nL,
+                 self.V, ptr(self.map), ptr(self.preclaim if self._pre_key is not None else None), ptr(self.E),
+                 ptr(self.Em), ptr(self.Ev), d, *self._replay_args(), sst.cuda_stream)
+        _events_end(ev, sst)
+
+    def _fold_duplicates(self, s: _Step, gv, lp1: int, in_sums: bool, stream: int) -> None:
+        """Float-atomic mode: the duplicates' gradients summed into extra[claimer] -- and (in_sums) the
+        table part of the clip norm right after the fold, on the fold's stream."""
+        n_ent = s.B * (s.L + 1)
+        call("fbn_sparse_fixup_dup", ptr(self.dup), n_ent, ptr(gv), ptr(self.extra), ptr(self.slot_row), lp1,
+             self.d, stream)
+        if in_sums:
+            call("fbn_sumsq_sparse_norms", ptr(self.gnorm), ptr(gv), ptr(self.extra), ptr(self.slot_row), lp1,
+                 n_ent, self.d, ptr(self.sumsq), None, None, 0, stream)
+
+    def _clip_norm_local(self, s: _Step, gsrc, n_ent: int) -> None:
+        """clip_grad_norm_(10) when the sum launch did not take the squares: the table gradient's and
+        the dense gradients' (final here) sums of squares in one launch -- two without a history."""
+        if s.L > 0:
+            call("fbn_sumsq_sparse_norms", ptr(self.gnorm), ptr(gsrc[0]), ptr(gsrc[1]), ptr(self.slot_row), gsrc[2],
+                 n_ent, self.d, ptr(self.sumsq), ptr(self.fx), ptr(self.flat_g), self.n_dense, s.st)
+        else:
+            call("fbn_sumsq_sparse", ptr(gsrc[0]), ptr(gsrc[1]), ptr(self.slot_row), gsrc[2], n_ent, self.d,
+                 ptr(self.sumsq), s.st)
+            call("fbn_sumsq", ptr(self.flat_g), self.n_dense, None, 0, ptr(self.sumsq), s.st)
+
+    # ---- launches of the sharded step
+    def _w16_on_side(self, s: _Step):
+        """The step's bf16 weight images (they depend only on the weights the previous step wrote) on
+        the side stream; returns the event main waits for before the forward."""
+        _lib.wait_stream(self.side, s.main)
+        with torch.cuda.stream(self.side):
+            self.acts["w16"] = ops.bf16_weights(self.p, self.d, self.acts, self.side.cuda_stream,
+                                                x=s.batch["item_emb_d128"])
+        ev = torch.cuda.Event()
+        _lib.record_event(ev, self.side)
+        return ev
+
+    def _owner_catchup(self, s: _Step, n_ent: int) -> None:
+        """Host-split form, lazy table Adam: the rows the owner just claimed brought up to date before
+        the gather reads them; then the rolling window."""
+        ev = _events(s.probe, "adam_catchup")
+        call("fbn_adam_catchup", ptr(self.E), ptr(self.Em), ptr(self.Ev), self.rows_local, self.d,
+             ptr(self.slot_row), n_ent, ptr(self.map), self.lazy_window, 1, *self._replay_args(), s.st)
+        _events_end(ev)
+        self._window(s, self._fork_side(s))
+
+    def _owner_claim_catchup(self, s: _Step, ids, n: int) -> None:
+        """Fixed-capacity form: claims + claimed-row catch-up in one launch, the claims decided by the
+        pre-claim tags the previous step's owner prefetch posted for this very routing (those with a
+        tag of this step; the rest by CAS); then the rolling window."""
+        ev = _events(s.probe, "adam_catchup")
+        pre = self.row_state.view(torch.int64)[:, 0] if self.prefetch_owner else None
+        call("fbn_adam_owner_claim_catchup", ptr(ids), n, int(self.rank == 0), ptr(self.map),
+             ptr(self.slot_row), ptr(pre), ptr(self.E), ptr(self.Em), ptr(self.Ev), self.rows_local, self.d,
+             self.lazy_window, *self._replay_args(), s.st)
+        _events_end(ev)
+        self._window(s, self._fork_side(s))
+
+    def _route_ahead(self, s: _Step, fwd_ev) -> None:
+        """The next batch routed on the side stream (RowExchange.prepare, after this step's row
+        exchange) and, lazy table Adam at d >= 128, its requested rows caught up ahead at the owner
+        (tagged pre-claims + the four-row replay engine)."""
+        x, nb = self.xchg, s.next_batch
+        own = self.prefetch_owner and self.table_adam == "lazy"
+        x.prepare(nb["item_id"], nb.get("item_seq"), self.err, send_rows=own, after=fwd_ev)
+        if own and x.next_lids is not None:
+            # after this step's claims and window (self.side), once the requests arrived
+            _lib.wait_stream(self.side, x.side)
+            ev = _events(s.probe, "adam_prefetch", self.side)
+            call("fbn_adam_prefetch_rows", ptr(x.next_lids), x.next_lids.numel(), int(self.rank == 0),
+                 self.rows_local, ptr(self.map), ptr(self.row_state.view(torch.int64)[:, 0]), ptr(self.E),
+                 ptr(self.Em), ptr(self.Ev), self.d, *self._replay_args(), self.side.cuda_stream)
+            _events_end(ev, self.side)
+            x.next_lids.record_stream(self.side)
+
+    def _owner_fold(self, s: _Step, sendbuf):
+        """The gradient-row exchange and the owner's duplicate fold: one received row per entry --
+        straight into this step's deferred-gradient ring slot when it fits, else a buffer of its own
+        and the rows applied at the step end.  Returns (gsrc, n_ent, defer_now, fold_done)."""
+        x, d, st = self.xchg, self.d, s.st
+        n_ent = x.n_recv
+        if x.fc_active:
+            # fixed-capacity form: the rows arrive in the fixed wire buffer; deferred, they move
+            # into ring slot step % ring_n chosen on the device (a replayed step program gets the
+            # right slot), and the readers take them through the slot's pointer cell
+            wire = x.backward_finish() if x._pending is not None else x.backward(sendbuf)
+            defer_now = self.deferred and n_ent <= self.ring_cap
+            # (this rank's own block was not sent: its rows are read from the send buffer itself)
+            lo, cnt = x.fc_self_rows
+            if self._fc_extra is None or self._fc_extra.shape[0] < n_ent:
+                self._fc_extra = _lib.persistent(
+                    lambda: torch.zeros((n_ent, d), dtype=torch.float32, device=self.device))
+            if defer_now:
+                ring, ring_n, stride = self.ring, self._ring_n_arg(), self._ring_stride()
+            else:
+                if self._fc_grad is None or self._fc_grad.shape[0] < n_ent:
+                    self._fc_grad = _lib.persistent(
+                        lambda: torch.empty((n_ent, d), dtype=torch.float32, device=self.device))
+                ring, ring_n, stride = self._fc_grad, 1, n_ent * d
+            rb = FBN_GRAD_BF16 if (defer_now and self.ring_bf16) else 0
+            # the widen into the ring slot and the duplicate fold in one pass: a claimer's row is
+            # stored, a duplicate's added into extra[claimer] (flagged; applied at the tail); the
+            # claimers' squares summed on the way (the flagged ones corrected by the norm).  Deterministic:
+            # the duplicates go to the fixed-point accumulator, extra becomes the FULL row gradient
+            fx = self._fold_bufs(n_ent)
+            call("fbn_owner_fold", ptr(x.recv_ids), n_ent, self.rank, ptr(self.map), ptr(self.slot_row),
+                 ptr(wire), int(wire.dtype == torch.bfloat16), ptr(x.fc_send) if cnt else None, lo, cnt,
+                 ptr(ring), ring_n, stride, ptr(self.step_dev), ptr(self.ring_cell), ptr(self._fc_extra), d,
+                 ptr(self._fc_part), ptr(fx), st)
+            gsrc = (self.ring_cell, self._fc_extra, 1 | FBN_GRAD_CELL | rb | (FBN_GRAD_FULL if fx is not None else 0))
+            return gsrc, n_ent, defer_now, True
+        slot = self._grad_slot()
+        if x._pending is not None:          # issued right after the fields backward
+            grows = x.backward_finish()
+        else:
+            grows = x.backward(sendbuf, out=slot)
+        g16 = grows.dtype == torch.bfloat16          # received straight into a bf16 ring slot
+        if (self.deterministic or g16) and n_ent > 0:
+            # the host-split form (calibration steps, overflow fallbacks): the owner fold in
+            # place over the received rows (the claimer's row is rewritten with itself; ring_n
+            # 1, the cell -> grows) -- deterministic (fixed point), or a bf16 ring slot (no
+            # float atomics into bf16 rows: the duplicates go to extra)
+            fx = self._fold_bufs(n_ent)
+            call("fbn_owner_fold", ptr(x.recv_ids), n_ent, self.rank, ptr(self.map), ptr(self.slot_row),
+                 ptr(grows), int(g16), None, 0, 0, ptr(grows), 1 | (FBN_RING_BF16 if g16 else 0), n_ent * d,
+                 ptr(self.step_dev), ptr(self.ring_cell), ptr(self._fc_extra), d, ptr(self._fc_part), ptr(fx),
+                 st)
+            gsrc = (self.ring_cell, self._fc_extra, 1 | FBN_GRAD_CELL | (FBN_GRAD_BF16 if g16 else 0) |
+                    (FBN_GRAD_FULL if fx is not None else 0))
+            return gsrc, n_ent, slot is not None, True
+        call("fbn_sparse_fixup", None, None, ptr(x.recv_ids), n_ent, 0, self.V, self.rank, ptr(self.map),
+             ptr(grows), None, ptr(self.slot_row), 1, d, st)
+        return (grows, None, 1), n_ent, slot is not None, False
+
+    def _clip_norm_sharded(self, s: _Step, gsrc, n_ent: int, fold_done: bool, dense_work) -> None:
+        """clip_grad_norm_(10): dense grads (identical on every rank after the all-reduce) + disjoint
+        table shards -- this shard's table sum of squares, then ONE all-reduce of the dense grads + the
+        loss + that sum, unpacked with the dense gradients' squares in one launch."""
+        d, st = self.d, s.st
+        if fold_done:
+            # the fold summed the claimers' own rows; only the flagged ones (duplicates) remain
+            call("fbn_sumsq_flagged", ptr(self.slot_row), n_ent, ptr(self.ring_cell), ptr(self._fc_extra), d,
+                 ptr(self._fc_part), ptr(self.sumsq_tab), ptr(self._fx_sh) if self.deterministic else None,
+                 int(bool(gsrc[2] & FBN_GRAD_BF16)), st)
+        else:
+            call("fbn_sumsq_sparse", ptr(gsrc[0]), ptr(gsrc[1]), ptr(self.slot_row), gsrc[2], n_ent, d,
+                 ptr(self.sumsq_tab), st)
+        o = self.n_dense
+        call("fbn_pack_extras", ptr(self.loss), ptr(self.sumsq_tab), ptr(self.flat_g_ext[o:]), st)
+        if dense_work is not None:
+            dist.all_reduce(self.flat_g_ext[o:o + 2], group=self.coll.group)
+            dense_work.wait()
+        else:
+            self.coll.allreduce_(self.flat_g_ext[:o + 2])
+        call("fbn_unpack_sumsq", ptr(self.flat_g_ext[o:]), ptr(self.loss), ptr(self.flat_g), o, ptr(self.sumsq), st)
 
     # ------------------------------------------------------------------ step programs (native step driver)
     def record_program(self, batch: Dict[str, torch.Tensor], labels: torch.Tensor,
@@ -1251,6 +1152,12 @@ class FiBiNETTrainer:
             return (None, None, None, 0, 0)
         return (ptr(self.pend), ptr(self.ring), ptr(self.coef_hist), self._ring_stride(), self._ring_n_arg())
 
+    def _replay_args(self):
+        """The argument tail every kernel that replays a row's Adam steps takes before its stream:
+        (last, sched, step, wd, beta2, eps, *_pend_args(), decoupled)."""
+        return (ptr(self.last), ptr(self.sched), ptr(self.step_dev), self.wd_g, self.beta2, self.eps,
+                *self._pend_args(), int(self.decoupled))
+
     def close(self) -> None:
         """Destroy the native RCCL communicators (the step's and the routing one) and their proxy
         threads; the trainer cannot step at N > 1 afterwards.  Idempotent."""
@@ -1268,9 +1175,8 @@ class FiBiNETTrainer:
     def flush(self) -> None:
         """Bring every table row up to the current step (lazy table Adam); a no-op when eager."""
         if self.table_adam == "lazy":
-            call("fbn_adam_flush", ptr(self.E), ptr(self.Em), ptr(self.Ev), self.rows_local, self.d, ptr(self.last),
-                 ptr(self.sched), ptr(self.step_dev), self.wd_g, self.beta2, self.eps, *self._pend_args(),
-                 int(self.decoupled), _lib.stream_handle(self.device))
+            call("fbn_adam_flush", ptr(self.E), ptr(self.Em), ptr(self.Ev), self.rows_local, self.d,
+                 *self._replay_args(), _lib.stream_handle(self.device))
 
     def _bn_from_rank0(self) -> None:
         """Per-rank BatchNorm (sync_bn=False) at N > 1: evaluation uses rank 0's running statistics

@@ -69,6 +69,20 @@ def test_library_reads_only_documented_environment():
                           "FBN_GROUP_SPLIT_DIV", "FBN_GROUP_W4"}
 
 
+def test_trainer_reads_only_documented_environment():
+    """What the environment can change in the trainer is written down: the FBN_* names trainer.py
+    passes to os.environ.get are exactly the rows of INTEGRATION.md's trainer table, so a switch
+    cannot appear (or come back) without its row, nor a row outlive its switch."""
+    src = open(os.path.join(ROOT, "ctr_recommendation_amd", "trainer.py")).read()
+    read = set(re.findall(r'os\.environ\.get\(\s*"(FBN_[A-Z0-9_]+)"', src))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = doc.split("### Environment variables the trainer reads", 1)[1].split("\n### ", 1)[0]
+    documented = set(re.findall(r"^\| `(FBN_[A-Z0-9_]+)` \|", section, flags=re.M))
+    assert read and read == documented, (sorted(read - documented), sorted(documented - read))
+    # no other way into the environment: every access in trainer.py is one of those os.environ.get calls
+    assert len(re.findall(r"environ|getenv", src)) == len(re.findall(r'os\.environ\.get\(\s*"FBN_', src))
+
+
 def test_wgrad_group_split_fills_two_workgroups_per_cu(monkeypatch):
     """The grouped weight-gradient launch's K-slabs (host planning only): by default 3/4 of the
     single launches' slabs, rounded, so C3's four problems (dWa 512 x 1920, dWb 256 x 512, the

@@ -3,7 +3,7 @@ ops), alternating blocks of K steps per arm for R rounds on one trainer at stead
 the median ms/step per arm (AB_ZIPF=s: Zipf(s) ids).  Usage: python tools/ab_step.py ARM [ARM ...] with ARM =
 name:module.GLOBAL=value[;module.GLOBAL=value...] ('base' = no change; module env = an
 environment variable the library reads per call: the table in INTEGRATION.md lists them), e.g.
-  python tools/ab_step.py base claim_main:trainer._CLAIM_ON_SIDE=False w4:env.FBN_GROUP_W4=1"""
+  python tools/ab_step.py base wgrad_early:trainer._WGRAD_EARLY=True w4:env.FBN_GROUP_W4=1"""
 import os
 import sys
 import time
