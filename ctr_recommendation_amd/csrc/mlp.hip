@@ -214,22 +214,33 @@ __global__ void bn_mean_kernel(const double* sum, double ntot, int C, double* me
   if (c < C) mean[c] = sum[c] / ntot;
 }
 
-// finalize BN train stats from the (global) sum of squared deviations: invstd, float mean,
-// running-stat update (momentum, unbiased var)
+// The float32 end of every statistics finalize, from column c's f64 mean mu and sum of squared
+// deviations q over ntot rows: float mean, invstd, running-stat update (momentum, unbiased var).
+// One function for bn_finalize_kernel, bn_tile_finalize_kernel and bn_moments_finalize_kernel, with
+// contraction off (each product rounded, then the sum -- the single-process form's arithmetic): left
+// to the compiler, one kernel fused momentum * unb into the sum and another did not, and the forms'
+// running statistics differed in the last bit.
+__device__ __forceinline__ void bn_stats_store(double q, double mu, double ntot, int c, float* mean, float* invstd,
+                                               float* run_mean, float* run_var, float momentum, float eps,
+                                               int update_running) {
+#pragma clang fp contract(off)
+  const float var_b = (float)(q / ntot);
+  mean[c] = (float)mu;
+  invstd[c] = 1.f / sqrtf(var_b + eps);
+  if (update_running) {
+    const float unb = ntot > 1.0 ? (float)(q / (ntot - 1.0)) : var_b;
+    run_mean[c] = momentum * (float)mu + (1.f - momentum) * run_mean[c];
+    run_var[c] = momentum * unb + (1.f - momentum) * run_var[c];
+  }
+}
+
+// finalize BN train stats from the (global) sum of squared deviations
 __global__ void bn_finalize_kernel(const double* m2, const double* mean_d, double ntot, int C, float* mean,
                                    float* invstd, float* run_mean, float* run_var, float momentum, float eps,
                                    int update_running) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const double s = m2[c];
-  const float var_b = (float)(s / ntot);
-  mean[c] = (float)mean_d[c];
-  invstd[c] = 1.f / sqrtf(var_b + eps);
-  if (update_running) {
-    const float unb = ntot > 1.0 ? (float)(s / (ntot - 1.0)) : var_b;
-    run_mean[c] = momentum * (float)mean_d[c] + (1.f - momentum) * run_mean[c];
-    run_var[c] = momentum * unb + (1.f - momentum) * run_var[c];
-  }
+  bn_stats_store(m2[c], mean_d[c], ntot, c, mean, invstd, run_mean, run_var, momentum, eps, update_running);
 }
 
 __global__ void bn_eval_params_kernel(const float* run_mean, const float* run_var, float* mean, float* invstd,
@@ -756,16 +767,7 @@ __global__ void bn_tile_finalize_kernel(const float* __restrict__ part, int T, i
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-  if (lane == 0) {
-    const float var_b = (float)(q / ntot);
-    mean[c] = (float)mu;
-    invstd[c] = 1.f / sqrtf(var_b + eps);
-    if (update_running) {
-      const float unb = ntot > 1.0 ? (float)(q / (ntot - 1.0)) : var_b;
-      run_mean[c] = momentum * (float)mu + (1.f - momentum) * run_mean[c];
-      run_var[c] = momentum * unb + (1.f - momentum) * run_var[c];
-    }
-  }
+  if (lane == 0) bn_stats_store(q, mu, ntot, c, mean, invstd, run_mean, run_var, momentum, eps, update_running);
 }
 
 // SyncBN (multi-GPU) forward statistics with ONE all-reduce per layer: each rank turns its
@@ -799,14 +801,7 @@ __global__ void bn_moments_finalize_kernel(const double* __restrict__ mom, doubl
   const double mu = mom[c] / ntot;
   double q = mom[C + c] - mom[c] * mu;
   if (q < 0.0) q = 0.0;
-  const float var_b = (float)(q / ntot);
-  mean[c] = (float)mu;
-  invstd[c] = 1.f / sqrtf(var_b + eps);
-  if (update_running) {
-    const float unb = ntot > 1.0 ? (float)(q / (ntot - 1.0)) : var_b;
-    run_mean[c] = momentum * (float)mu + (1.f - momentum) * run_mean[c];
-    run_var[c] = momentum * unb + (1.f - momentum) * run_var[c];
-  }
+  bn_stats_store(q, mu, ntot, c, mean, invstd, run_mean, run_var, momentum, eps, update_running);
 }
 
 // Backward: chunk reduce of the three partial sums + the finalize of bn_bwd_finalize_kernel,
@@ -1375,9 +1370,11 @@ extern "C" int fbn_bn_act_head_fwd(const float* X, float* Y, int B, int C, const
   if (p_drop > 0.f && !rng && !mask_in) { fbn_set_error("bn_act: dropout needs an rng state or a mask"); return FBN_ERR_ARG; }
   if (bwd_part && !gout) { fbn_set_error("bn_act_head: backward partials need labels / gout"); return FBN_ERR_ARG; }
   if (bwd_part) {
-    // the row chunks of fbn_bn_bwd_fused, so its reduce reads these partials as its own
+    // the row chunks of fbn_bn_bwd_fused, so its reduce reads these partials as its own: all nch of
+    // them are launched (as bn_bwd_partial4's grid) -- past B = 8192 nch is capped, rpc is rounded up
+    // and the last chunks hold no rows; they skip the row loop and store zeros for the reduce to add
     const int nch = bn_bwd_chunks(B, C), rpc = (B + nch - 1) / nch;
-    fbn_launch(bn_act_head_bwd4_kernel, dim3(1, fbn_cdiv(B, rpc)), dim3(256), 0, (hipStream_t)stream, X, Y, B,
+    fbn_launch(bn_act_head_bwd4_kernel, dim3(1, nch), dim3(256), 0, (hipStream_t)stream, X, Y, B,
                C, rpc, mean, invstd, g, b, p_drop, rng, stream_id, mask_out, mask_in,
                HeadArgs{hw, hbias, logits, probs, labels, loss_terms, gout, denom}, bwd_part, bwd_scale);
     FBN_CHECK_LAUNCH();

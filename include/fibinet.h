@@ -228,7 +228,8 @@ int fbn_bn_stats(const float* X, int B, int C, float* mean, float* invstd, float
  * out = column sums of squared deviations about mean_d (Chan merge, f64). */
 int fbn_bn_tile_stats(const float* part, int M, int C, const double* mean_d, double* out_d, void* stream);
 /* Single-process form of the above + fbn_bn_mean + fbn_bn_finalize in one launch (same f64
- * operations in the same order; the multi-GPU path needs the all-reduces in between). */
+ * operations in the same order and the same float32 finalize: bit-identical outputs; the multi-GPU
+ * path needs the all-reduces in between). */
 /* SyncBN (multi-GPU) with one all-reduce per layer: per-rank raw moments out[2C] = {sum x,
  * sum x^2} from the tile partials, all-reduced by the caller, then the finalize. */
 int fbn_bn_tile_moments(const float* part, int M, int C, double* out_d, void* stream);
@@ -250,7 +251,8 @@ int fbn_bn_act_fwd_img(const float* X, float* Y, int B, int C, const float* mean
 /* fbn_bn_act_fwd of the last hidden layer (C = 256) fused with fbn_head_fwd (same outputs).
  * bwd_part (optional, with labels / gout; fbn_bn_bwd_chunks(B, C) * 3 * C doubles): the first pass
  * of this layer's BN backward (rank-1 source gout x hw, dropout scale bwd_scale), handed to
- * fbn_bn_bwd_fused as part_pre. */
+ * fbn_bn_bwd_fused as part_pre.  Every one of the fbn_bn_bwd_chunks(B, C) chunks is written (a chunk
+ * past the last row holds zeros), so the buffer needs no initialisation. */
 int fbn_bn_act_head_fwd(const float* X, float* Y, int B, int C, const float* mean, const float* invstd, const float* g,
                         const float* b, float p_drop, const unsigned long long* rng, unsigned stream_id,
                         unsigned char* mask_out, const unsigned char* mask_in, const float* hw, const float* hbias,

@@ -488,7 +488,7 @@ def test_gemm_bn_bwd_part_epilogue(hip_device, M):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("B", [8192, 1000, 37])
+@pytest.mark.parametrize("B", [8192, 1000, 37, 8200])
 def test_fused_head_four_rows_per_wave(hip_device, B):
     """fbn_bn_act_head_fwd with the BN2 backward's first pass (bn_act_head_bwd4_kernel, four rows
     per wave): its forward outputs equal the head launch without the backward pass bit for bit,
