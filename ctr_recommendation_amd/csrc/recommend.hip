@@ -11,6 +11,9 @@
 //                   operands handed to the bilinear / MLP kernels are the same bits.
 // fbn_rec_topk turns a chunk's logits into 64-bit keys {ordered logit, ~catalogue position} and keeps
 // each user's K largest across chunks: integer compares only, no float atomics, no sort of U x M.
+// fbn_rec_rank counts, in the same key order, how many eligible candidates of a user's full row of
+// logits lie above one held-out target; fbn_rank_hist adds such ranks to an integer record from which
+// the host derives HR / NDCG / MRR@K.
 #include "common.h"
 #include "fields_common.h"
 
@@ -422,6 +425,152 @@ extern "C" int fbn_rec_topk(const float* logits, int U, int m0, int Mc, const in
   }
   a.mode = 1;
   fbn_launch(rec_topk_kernel, dim3(1, U), dim3(256), 0, st, a);
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}
+
+// ------------------------------------------------------------------------------ rank of a held-out item
+// rank[u] = 1 + the number of eligible candidates whose rec_key is above the target's, over the user's
+// whole row of logits [U][ld]: the place fbn_rec_topk would give the target, without selecting.  One
+// workgroup per (user, REC_SEG candidates) counts two predicates with wave ballots and adds its two
+// integers to rank[u] / n_eligible[u]: integer atomics, so the sums do not depend on launch order.
+struct RecRankArgs {
+  const float* logits;         // [U][ld]
+  const int64_t* item_id;      // [M]
+  const int64_t* item_seq;     // [U][L] or null
+  const int64_t* target_pos;   // [U]
+  int* rank; int* n_eligible;  // [U]
+  unsigned* status;
+  int U, M, ld, L, exclude;
+};
+
+// a target is ranked when it names a catalogue position whose item is not the padding item
+__device__ __forceinline__ bool rec_rank_valid(const RecRankArgs& p, long long t) {
+  return t >= 0 && t < p.M && p.item_id[t] != 0;
+}
+
+__global__ void __launch_bounds__(256) rec_rank_init_kernel(RecRankArgs p) {
+  const int u = blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= p.U) return;
+  const long long t = p.target_pos[u];
+  const bool valid = rec_rank_valid(p, t);
+  if (valid) {
+    bool nan;
+    rec_key(p.logits[(size_t)u * p.ld + t], (unsigned)t, nan);
+    if (nan) atomicOr(p.status, 1u);
+  }
+  p.rank[u] = valid ? 1 : 0;
+  p.n_eligible[u] = 0;
+}
+
+__global__ void __launch_bounds__(256) rec_rank_kernel(RecRankArgs p) {
+  __shared__ long long hist[FBN_MAX_L];
+  __shared__ unsigned long long tkey_s;
+  __shared__ int valid_s;
+  __shared__ int cnt[4][2];
+  const int t = threadIdx.x, u = blockIdx.y, seg = blockIdx.x;
+  const int L = p.item_seq ? p.L : 0;
+  const int base = seg * REC_SEG, n = min(REC_SEG, p.M - base);
+  const long long tp = p.target_pos[u];
+  if (t < L) hist[t] = p.item_seq[(size_t)u * L + t];
+  if (t == 0) {
+    const bool valid = rec_rank_valid(p, tp);
+    bool nan;
+    tkey_s = valid ? rec_key(p.logits[(size_t)u * p.ld + tp], (unsigned)tp, nan) : 0ull;
+    valid_s = valid;
+  }
+  __syncthreads();
+  const unsigned long long tkey = tkey_s;
+  const bool valid = valid_s != 0;
+  int above = 0, elig = 0;                                  // wave-uniform
+  for (int i0 = 0; i0 < n; i0 += 256) {
+    const int i = i0 + t;
+    bool e = false, g = false;
+    if (i < n) {
+      const long long m = (long long)base + i;
+      e = true;
+      if (p.exclude) {
+        const long long id = p.item_id[m];
+        bool in_hist = false;
+        for (int l = 0; l < L; ++l) in_hist |= hist[l] != 0 && hist[l] == id;
+        e = id != 0 && (m == tp || !in_hist);             // the target stays eligible inside its own history
+      }
+      bool nan;
+      g = e && valid && m != tp && rec_key(p.logits[(size_t)u * p.ld + m], (unsigned)m, nan) > tkey;
+    }
+    elig += __popcll(__ballot(e));
+    above += __popcll(__ballot(g));
+  }
+  if ((t & 63) == 0) { cnt[t >> 6][0] = above; cnt[t >> 6][1] = elig; }
+  __syncthreads();
+  if (t == 0) {
+    const int a = cnt[0][0] + cnt[1][0] + cnt[2][0] + cnt[3][0];
+    const int e = cnt[0][1] + cnt[1][1] + cnt[2][1] + cnt[3][1];
+    if (a) atomicAdd(p.rank + u, a);
+    if (e) atomicAdd(p.n_eligible + u, e);
+  }
+}
+
+extern "C" int fbn_rec_rank(const float* logits, int ld, int U, int M, const int64_t* item_id,
+                            const int64_t* item_seq, int L, int exclude, const int64_t* target_pos, int* rank,
+                            int* n_eligible, unsigned* status, void* stream) {
+  if (L < 0 || L > FBN_MAX_L) {
+    fbn_set_error("fbn_rec_rank: history length L must be in 0..32");
+    return FBN_ERR_ARG;
+  }
+  if (U < 0 || U > 65535 || M < 0 || ld < M) {
+    fbn_set_error("fbn_rec_rank: need 0 <= U <= 65535, M >= 0 and ld >= M");
+    return FBN_ERR_ARG;
+  }
+  if (U == 0) return FBN_OK;
+  RecRankArgs a;
+  a.logits = logits; a.item_id = item_id; a.item_seq = L > 0 ? item_seq : nullptr; a.target_pos = target_pos;
+  a.rank = rank; a.n_eligible = n_eligible; a.status = status; a.U = U; a.M = M; a.ld = ld; a.L = L;
+  a.exclude = exclude;
+  hipStream_t st = (hipStream_t)stream;
+  fbn_launch(rec_rank_init_kernel, dim3(fbn_cdiv(U, 256)), dim3(256), 0, st, a);
+  FBN_CHECK_LAUNCH();
+  const int nseg = fbn_cdiv(M, REC_SEG);
+  if (nseg > 0) {
+    fbn_launch(rec_rank_kernel, dim3(nseg, U), dim3(256), 0, st, a);
+    FBN_CHECK_LAUNCH();
+  }
+  return FBN_OK;
+}
+
+// ------------------------------------------------------------------------------ rank record
+// rec[0] ranks <= 0 (not ranked), rec[r] ranks == r for 1 <= r <= 256, rec[257] ranks > 256,
+// rec[258] the sum of the ranks >= 1, rec[259] their number: a histogram per workgroup in LDS, then
+// one integer atomic per non-empty word.  No floating point: HR / NDCG / MRR@K are host functions of
+// these integers, additive over calls.
+#define REC_RANK_WORDS 260
+
+__global__ void __launch_bounds__(256) rank_hist_kernel(const int* rank, long long n, unsigned long long* rec) {
+  __shared__ unsigned long long h[REC_RANK_WORDS];
+  const int t = threadIdx.x;
+  for (int i = t; i < REC_RANK_WORDS; i += 256) h[i] = 0ull;
+  __syncthreads();
+  unsigned long long sum = 0ull, ranked = 0ull;
+  for (long long i = (long long)blockIdx.x * 256 + t; i < n; i += (long long)gridDim.x * 256) {
+    const int r = rank[i];
+    atomicAdd(&h[r < 1 ? 0 : (r > 256 ? 257 : r)], 1ull);
+    if (r >= 1) { sum += (unsigned long long)r; ++ranked; }
+  }
+  if (ranked) { atomicAdd(&h[258], sum); atomicAdd(&h[259], ranked); }
+  __syncthreads();
+  for (int i = t; i < REC_RANK_WORDS; i += 256)
+    if (h[i]) atomicAdd(rec + i, h[i]);
+}
+
+extern "C" int fbn_rank_hist(const int* rank, long long n, unsigned long long* rec, void* stream) {
+  if (n < 0) {
+    fbn_set_error("fbn_rank_hist: negative n");
+    return FBN_ERR_ARG;
+  }
+  if (n == 0) return FBN_OK;
+  const long long blocks = (n + 255) / 256;
+  const dim3 grid((unsigned)(blocks > 1024 ? 1024 : blocks));
+  fbn_launch(rank_hist_kernel, grid, dim3(256), 0, (hipStream_t)stream, rank, n, rec);
   FBN_CHECK_LAUNCH();
   return FBN_OK;
 }

@@ -11,7 +11,9 @@ fields are composed from two caches (csrc/recommend.hip):
 and the rest of the forward (SENET, bilinear, MLP, head) is ``ops.forward``'s own launches on the pair
 rows, chunk by chunk, so a score is what the eval forward gives for that pair.  ``topk`` feeds every
 chunk's logits to ``fbn_rec_topk``, which carries each user's K best as integer keys: no score ever
-reaches the host and the U x M matrix is never sorted.
+reaches the host and the U x M matrix is never sorted.  ``rank`` counts, in the same order, how many
+eligible items lie above one held-out item per user (``fbn_rec_rank`` on one sweep's logits), and
+``evaluate`` turns such ranks into HR / NDCG / MRR@K through ``rank_metrics.RankMetrics``.
 
 Single device, bilinear "all"; a row-sharded table is out of scope.
 """
@@ -85,7 +87,7 @@ class Recommender:
                 tuple(self._x.shape) != (self.M, 128):
             raise ValueError("catalogue columns must be [M] and item_emb_d128 [M, 128] with M >= 1")
         self.err = torch.zeros(1, dtype=torch.int32, device=dev)
-        # bit 0: a NaN logit reached the selection (it ranks below every number)
+        # bit 0: a NaN logit reached the selection (it ranks below every number), or was a ranked target's
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         self._acts: Dict[int, Dict] = {}
         self._probe: Optional[Dict[str, list]] = None      # tools/recommend_bench.py: ops.forward's kernel probes
@@ -131,6 +133,29 @@ class Recommender:
             call("fbn_rec_item_cache", ptr(self.cat["item_id"]), ptr(self.cat["likes_level"]),
                  ptr(self.cat["views_level"]), ptr(hmm), ptr(p["mm_proj.1.weight"]), ptr(p["mm_proj.1.bias"]),
                  ops.LN_EPS, int(p["cate_emb.weight"].shape[0]), self.V, ptr(self.cache), ptr(self.err), self.M, d, st)
+            self._build_positions()
+
+    def _build_positions(self) -> None:
+        """self._pos [V] int32: id -> smallest catalogue position holding it, -1 for an id the catalogue
+        lacks (torch ops on the device; a catalogue id outside [0, V) has no entry)."""
+        ids = self.cat["item_id"]
+        pos = torch.arange(self.M, dtype=torch.int64, device=self.device)
+        ok = (ids >= 0) & (ids < self.V)
+        ids, pos = ids[ok], pos[ok]
+        ids, order = torch.sort(ids, stable=True)                 # equal ids stay in position order
+        first = torch.ones_like(ids, dtype=torch.bool)
+        first[1:] = ids[1:] != ids[:-1]
+        self._pos = torch.full((self.V,), -1, dtype=torch.int32, device=self.device)
+        self._pos[ids[first]] = pos[order][first].to(torch.int32)   # distinct indices: no write order to depend on
+
+    def positions(self, item_ids: torch.Tensor) -> torch.Tensor:
+        """Catalogue positions (int64, the shape of ``item_ids``) of item ids: the smallest position when
+        the catalogue repeats an id, -1 for an id that is not in the catalogue or lies outside [0, V).
+        No host sync, and no id faults."""
+        ids = torch.as_tensor(item_ids).to(self.device).long()
+        ok = (ids >= 0) & (ids < self.V)
+        found = self._pos[ids.clamp(0, self.V - 1)].long()
+        return torch.where(ok, found, torch.full_like(found, -1))
 
     def check_ids(self) -> None:
         """Raise the reference's IndexError if any id seen since construction (or the last refresh)
@@ -196,10 +221,15 @@ class Recommender:
         with torch.cuda.device(self.device):
             st = _lib.stream_handle(self.device)
             _, hist, U, _ = self._hist(item_seq, st)
-            out = torch.empty((U, self.M), dtype=torch.float32, device=self.device)
-            for m0, Mc in self._chunks(U):
-                a = self._forward_chunk(hist, U, m0, Mc)
-                out[:, m0:m0 + Mc].copy_((a["logits"] if logits else a["probs"]).view(U, Mc))
+            out = self._sweep(hist, U, logits)
+        return out
+
+    def _sweep(self, hist, U: int, logits: bool) -> torch.Tensor:
+        """One catalogue sweep of the chunk loop collected into [U, M] (4 U M bytes)."""
+        out = torch.empty((U, self.M), dtype=torch.float32, device=self.device)
+        for m0, Mc in self._chunks(U):
+            a = self._forward_chunk(hist, U, m0, Mc)
+            out[:, m0:m0 + Mc].copy_((a["logits"] if logits else a["probs"]).view(U, Mc))
         return out
 
     @torch.no_grad()
@@ -232,3 +262,77 @@ class Recommender:
                      ptr(out["index"]) if last else None, ptr(out["item_id"]) if last else None,
                      ptr(out["logit"]) if last else None, ptr(out["prob"]) if last else None, ptr(self.status), st)
         return out
+
+    @torch.no_grad()
+    def rank(self, item_seq: Optional[torch.Tensor], target: torch.Tensor, *, exclude_history: bool = True,
+             by: str = "item_id", _status: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """The rank of one held-out item per user among the eligible catalogue items, in ``topk``'s
+        order: ``{"rank": int32 [U], "n_eligible": int32 [U]}``, rank 1 = ``topk``'s first place.
+        ``target`` [U] holds item ids (``by="item_id"``, mapped by :meth:`positions`) or catalogue
+        positions (``by="index"``); ``item_seq=None`` with one target is the cold user.  Eligibility is
+        ``topk``'s rule (exclude_history: no padding items, no items of the user's own history) except
+        that the target itself stays eligible when the history holds it.  A target that is not in the
+        catalogue, or is the padding item, gets rank 0 ("not ranked").
+
+        One catalogue sweep through the chunk loop into a [U, M] f32 buffer of logits -- 4 U M bytes,
+        23 MB for 64 users x 91,718 items -- then one ``fbn_rec_rank`` call: only logits of the same
+        sweep are compared.  Nothing is copied to the host and nothing synchronises; a
+        NaN logit at a ranked target sets bit 0 of ``status``, as a NaN does in ``topk``."""
+        if by not in ("item_id", "index"):
+            raise ValueError(f"by must be 'item_id' or 'index', not {by!r}")
+        dev = self.device
+        with torch.cuda.device(dev):
+            st = _lib.stream_handle(dev)
+            seq, hist, U, L = self._hist(item_seq, st)
+            tgt = torch.as_tensor(target).to(dev).long().reshape(-1)
+            if tgt.numel() != U:
+                raise ValueError(f"target holds {tgt.numel()} items for {U} users")
+            pos = (self.positions(tgt) if by == "item_id" else tgt).contiguous()
+            buf = self._sweep(hist, U, True)
+            out = {"rank": torch.empty(U, dtype=torch.int32, device=dev),
+                   "n_eligible": torch.empty(U, dtype=torch.int32, device=dev)}
+            call("fbn_rec_rank", ptr(buf), self.M, U, self.M, ptr(self.cat["item_id"]), ptr(seq), L,
+                 int(bool(exclude_history)), ptr(pos), ptr(out["rank"]), ptr(out["n_eligible"]),
+                 ptr(self.status if _status is None else _status), st)
+        return out
+
+    @torch.no_grad()
+    def evaluate(self, pairs, ks=(5, 10, 20), *, exclude_history: bool = True, max_users: Optional[int] = None,
+                 users_per_block: int = 64) -> Dict:
+        """HR@K, NDCG@K and MRR@K of ``topk`` over the full catalogue on held-out interactions.
+        ``pairs``: an iterable of (batch, labels) as ``FiBiNETTrainer.evaluate`` takes it; every row
+        with label 1 is one evaluation user with history ``batch["item_seq"]`` and held-out item
+        ``batch["item_id"]``, taken in order until ``max_users``.  The users go ``users_per_block`` at
+        a time through :meth:`rank` (4 * users_per_block * M bytes of logits) into a
+        :class:`RankMetrics` record on the device.  Selecting a batch's positive rows synchronises once
+        per batch; nothing else does until the record is read at the end.  Returns
+        ``RankMetrics.compute(ks)``; raises ValueError when a ranked target's logit was NaN, and
+        ``check_ids()``'s IndexError for an id outside its table."""
+        from .rank_metrics import RankMetrics, _check_ks
+        ks = _check_ks(ks)
+        upb = int(users_per_block)
+        if upb < 1:
+            raise ValueError("users_per_block must be positive")
+        left = None if max_users is None else int(max_users)
+        dev = self.device
+        metrics = RankMetrics(dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)     # this evaluation's own NaN flag
+        for batch, labels in pairs:
+            if left is not None and left <= 0:
+                break
+            rows = (labels.to(dev).reshape(-1) == 1).nonzero().reshape(-1)      # the per-batch sync
+            if left is not None:
+                rows = rows[:left]
+                left -= int(rows.numel())
+            if rows.numel() == 0:
+                continue
+            seq, tgt = batch["item_seq"].to(dev)[rows], batch["item_id"].to(dev).reshape(-1)[rows]
+            for r0 in range(0, int(rows.numel()), upb):
+                out = self.rank(seq[r0:r0 + upb], tgt[r0:r0 + upb], exclude_history=exclude_history, _status=status)
+                metrics.update(out["rank"])
+        self.status |= status
+        if int(status.item()) & 1:
+            raise ValueError("Recommender.evaluate: the logit of a ranked target is NaN")
+        result = metrics.compute(ks)
+        self.check_ids()
+        return result

@@ -713,6 +713,32 @@ size_t fbn_rec_topk_workspace_size(int U, int Mc, int K);
 int fbn_rec_topk(const float* logits, int U, int m0, int Mc, const int64_t* item_id, const int64_t* item_seq, int L,
                  int exclude, int K, unsigned long long* carry, void* ws, size_t ws_bytes, int64_t* out_index,
                  int64_t* out_item, float* out_logit, float* out_prob, unsigned* status, void* stream);
+/* fbn_rec_rank: the rank of one held-out target per user in that user's full row of logits [U][ld]
+ * (ld >= M; columns 0 .. M-1 are the catalogue positions: what the chunk loop produces for a whole
+ * sweep); replaces copying the U x M scores to the host and ranking there, or searching fbn_rec_topk's
+ * lists.  The order is fbn_rec_topk's key order and nothing else: key = {order-preserving image of
+ * the f32 logit, 0xFFFFFFFF - position}, so -0.0 lies below +0.0, a NaN below -inf, and equal logits go
+ * to the smaller position.  With t = target_pos[u] (a catalogue position; negative: not in the catalogue)
+ *   rank[u]       = 1 + #{m != t : eligible(u, m) and key(m) > key(t)}
+ *   n_eligible[u] = #{m : eligible(u, m)}
+ * eligible(u, m): exclude == 0: every m.  Otherwise fbn_rec_topk's rule -- item_id[m] != 0 and item_id[m]
+ * equals no non-padding id of item_seq[u] ([U][L], may be NULL) -- except that the target's own position
+ * stays eligible when its id is in the history.  t < 0, t >= M or item_id[t] == 0: rank[u] = 0 ("not
+ * ranked"; n_eligible[u] is still the count).  A ranked target whose own logit is NaN sets bit 0 of
+ * *status; NaNs elsewhere do not.  The call initialises rank and n_eligible.  0 <= L <= 32, ld >= M >= 0,
+ * 0 <= U <= 65535 (else FBN_ERR_ARG, checked on the host before any device work); U == 0 launches
+ * nothing.  Two launches: the initialisation, then per (user, 1024-candidate segment) ballot counts added
+ * with one integer atomic per workgroup and output -- no float arithmetic, so no dependence on launch order. */
+int fbn_rec_rank(const float* logits, int ld, int U, int M, const int64_t* item_id, const int64_t* item_seq, int L,
+                 int exclude, const int64_t* target_pos, int* rank, int* n_eligible, unsigned* status, void* stream);
+/* fbn_rank_hist: adds n ranks (fbn_rec_rank's output) to the record rec[FBN_RANK_REC_WORDS] (uint64, zeroed
+ * once by the caller); replaces a host loop over the ranks per batch.  rec[0]: ranks < 1 (not ranked);
+ * rec[r], 1 <= r <= 256: ranks equal to r; rec[257]: ranks above 256; rec[258]: the sum of the ranks >= 1;
+ * rec[259]: their number.  Integer atomics only: the record is exact, additive over calls (and over
+ * devices), and HR@K = sum_{r<=K} rec[r] / rec[259], NDCG@K = sum_{r<=K} rec[r] / log2(r + 1) / rec[259],
+ * MRR@K = sum_{r<=K} rec[r] / r / rec[259] (K <= 256) are host functions of it.  n == 0 launches nothing. */
+#define FBN_RANK_REC_WORDS 260
+int fbn_rank_hist(const int* rank, long long n, unsigned long long* rec, void* stream);
 
 /* ---------------------------------------------------------------- step programs (native step driver)
  * Replaces the Python loop body that issues one training step (src/train_fibinet.py:113-123): the

@@ -12,6 +12,12 @@ interleaved).  stage_ms: kernel spans of (a)'s stages summed over the chunks of 
 library's kernel probes; "forward" is the whole chunk forward, fields included).
 
     python tools/recommend_bench.py [--users 64] [--out profiles/recommend_vs_expanded.json]
+
+--rank-eval: the same shape and method for the rank evaluation, one target per user:
+  (a) rank_ms       Recommender.rank + RankMetrics.update: the sweep into a [U, M] buffer of logits,
+                    fbn_rec_rank, fbn_rank_hist
+  (b) topk_ms       Recommender.topk(k = 10) of the same users
+with (a)'s kernel spans per stage; written to profiles/recommend_rank_eval.json.
 """
 import argparse
 import json
@@ -33,6 +39,99 @@ def _span(probes):
     return sum(max(0.0, kp.elapsed_time()) for kp, _ in probes)
 
 
+def _timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    r = fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b), r
+
+
+def rank_eval(args, rec, seq, target):
+    """(a) rank() + RankMetrics.update vs (b) topk(k) of the same users; target: [U] catalogue positions."""
+    import ctr_recommendation_amd.rank_metrics as mmod
+    import ctr_recommendation_amd.recommend as rmod
+    dev, U, K = rec.device, seq.shape[0], args.k
+    metrics = mmod.RankMetrics(dev)
+
+    def ranking():
+        out = rec.rank(seq, target, by="index")
+        metrics.update(out["rank"])
+        return out
+
+    def selecting():
+        return rec.topk(seq, K)
+
+    ranking(), selecting()                                  # warm-up (allocations, bf16 images)
+    ta, tb = [], []
+    for _ in range(args.runs):                              # interleaved A/B
+        ta.append(_timed(ranking)[0])
+        t, top = _timed(selecting)
+        tb.append(t)
+    out = ranking()
+    rec.check_ids()
+    rank, index = out["rank"].cpu(), top["index"].cpu()
+    tpos = target.cpu()
+    agree = all((int(rank[u]) <= K) == (int(tpos[u]) in index[u].tolist()) for u in range(U) if int(rank[u]) >= 1)
+
+    # one probed run of (a): kernel spans per stage, summed over the chunks
+    stages, whole = {}, []
+    call0, mcall0, fwd0 = rmod.call, mmod.call, rec._forward_chunk
+
+    def probed_call(name, *a):
+        if name in ("fbn_rec_hist_pool", "fbn_rec_rank", "fbn_rank_hist"):
+            kp = _lib.KernelProbe()
+            stages.setdefault(name, []).append((kp, None))
+            try:
+                return call0(name, *a)
+            finally:
+                kp.done()
+        return call0(name, *a)
+
+    def probed_forward(*a):
+        kp = _lib.KernelProbe()
+        whole.append((kp, None))
+        try:
+            return fwd0(*a)
+        finally:
+            kp.done()
+
+    rmod.call = mmod.call = probed_call
+    rec._forward_chunk = probed_forward
+    ranking()
+    torch.cuda.synchronize()
+    rmod.call, mmod.call, rec._forward_chunk = call0, mcall0, fwd0
+    stage_ms = {"hist_pool": _span(stages["fbn_rec_hist_pool"]), "forward": _span(whole),
+                "rank": _span(stages["fbn_rec_rank"]), "rank_hist": _span(stages["fbn_rank_hist"])}
+    # the sweep's copies of each chunk's logits into the [U, M] buffer (torch's strided copy_), alone
+    chunks = list(rec._chunks(U))
+    n_chunks, (m0, Mc) = len(chunks), chunks[0]
+    full, chunk = torch.empty((U, rec.M), device=dev), torch.zeros(U * Mc, device=dev)
+
+    def copies():
+        for _ in range(n_chunks):
+            full[:, m0:m0 + Mc].copy_(chunk.view(U, Mc))
+
+    copies()
+    stage_ms["buffer_copies_event_ms"] = statistics.median(_timed(copies)[0] for _ in range(5))
+
+    ma, mb = statistics.median(ta), statistics.median(tb)
+    res = {"device": torch.cuda.get_device_name(dev), "users": U, "items": rec.M, "k": K, "d": rec.d,
+           "dtype": args.dtype, "chunk_rows": rec.chunk_rows, "chunks": n_chunks, "runs": args.runs,
+           "statistic": "median", "rank_ms": round(ma, 3), "topk_ms": round(mb, 3),
+           "ratio_rank_over_topk": round(ma / mb, 3), "rank_ms_min_max": [round(min(ta), 3), round(max(ta), 3)],
+           "topk_ms_min_max": [round(min(tb), 3), round(max(tb), 3)],
+           "logits_buffer_bytes": 4 * U * rec.M, "stage_ms": {k: round(v, 3) for k, v in stage_ms.items()},
+           "rank_agrees_with_topk": bool(agree), "metrics": metrics.compute((5, 10, 20))}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--users", type=int, default=64)
@@ -43,8 +142,12 @@ def main():
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--chunk-rows", type=int, default=None)
     ap.add_argument("--runs", type=int, default=RUNS)
-    ap.add_argument("--out", default=os.path.join("profiles", "recommend_vs_expanded.json"))
+    ap.add_argument("--rank-eval", action="store_true", help="time rank() + RankMetrics.update against topk")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join("profiles", "recommend_rank_eval.json" if args.rank_eval
+                                else "recommend_vs_expanded.json")
     dev = torch.device("cuda", 0)
     U, M, K, d, L, B = args.users, args.items, args.k, args.d, 20, args.batch
     cfg = {"embedding_dim": d, "vocab_size": M, "compute_dtype": args.dtype}
@@ -58,6 +161,8 @@ def main():
     seq[torch.rand((U, L), generator=g) < 0.3] = 0
     seq = seq.to(dev)
     rec = Recommender(model.state_dict(), cfg, cat, device=dev, chunk_rows=args.chunk_rows)
+    if args.rank_eval:
+        return rank_eval(args, rec, seq, torch.randint(0, M, (U,), generator=g).to(dev))
     catd = {k: v.to(dev) for k, v in rec.cat.items()}
     catd["item_emb_d128"] = rec._x
     fcfg = ops.FwdConfig(**{**rec.cfg.__dict__, "L": L})
@@ -77,21 +182,12 @@ def main():
     def serving():
         return rec.topk(seq, K, exclude_history=False)
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        a.record()
-        r = fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b), r
-
     serving(), expanded()                                   # warm-up (allocations, bf16 images)
     ta, tb = [], []
     for _ in range(args.runs):                              # interleaved A/B
-        t, ra = timed(serving)
+        t, ra = _timed(serving)
         ta.append(t)
-        t, rb = timed(expanded)
+        t, rb = _timed(expanded)
         tb.append(t)
     rec.check_ids()
     same = (ra["index"] == rb.indices).float().mean().item()
