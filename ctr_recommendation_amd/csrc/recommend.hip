@@ -14,6 +14,11 @@
 // fbn_rec_rank counts, in the same key order, how many eligible candidates of a user's full row of
 // logits lie above one held-out target; fbn_rank_hist adds such ranks to an integer record from which
 // the host derives HR / NDCG / MRR@K.
+// The *_list entry points run the same kernels over per-user candidate lists cand_pos [U][ldp] of
+// catalogue positions (negative: an empty slot): the pair's position is read through the list, and the
+// key's low word carries the slot -- the index into the user's list -- instead of the position.
+#include <cstdio>
+
 #include "common.h"
 #include "fields_common.h"
 
@@ -167,11 +172,68 @@ struct RecFieldArgs {
   void* c;                   // [P][ldc] float or bf16 (c16): cols [0,5D) <- V (optional)
   float* a_out;              // [P][6] (optional)
   int* err;
+  const int64_t* cand_pos;   // [U][ldp] per-user lists (the list kernel only)
   long long V;
-  int U, m0, Mc, ldc, R, n_cate, c16;
+  int U, m0, Mc, ldc, R, n_cate, c16;   // list kernel: m0 / Mc are the first slot c0 / the slot count Cc
+  int ldp, M;
 };
 
-template <int D>
+// Pair row b = (user u, catalogue position m), this lane's 4 columns q.  LIST: m < 0 is an empty slot --
+// no table or cache read, X1..X4 = 0 -- and the rest runs unchanged, so the row is the SENET of
+// (0, 0, 0, 0, hist[u]): defined operands for the GEMMs, and no flag.
+template <int D, bool LIST>
+__device__ __forceinline__ void rec_pair_row(const RecFieldArgs& p, int u, long long m, long long b, int q) {
+  constexpr int G = D / 4;
+  // ---------------- ids (validated as fbn_fields_fwd does: a bad id reads row 0 / a zero row)
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  f32x4 c1 = zero, c2 = zero, rit = zero, x4 = zero;
+  bool bad = false;
+  if (!LIST || m >= 0) {
+    long long item = p.item_id[m], lk = p.likes[m], vw = p.views[m];
+    if (lk < 0 || lk >= p.n_cate) { bad = true; lk = 0; }
+    if (vw < 0 || vw >= p.n_cate) { bad = true; vw = 0; }
+    if (item < 0 || item >= p.V) { bad = true; item = -1; }
+    c1 = *reinterpret_cast<const f32x4*>(p.cate + lk * D + 4 * q);
+    c2 = *reinterpret_cast<const f32x4*>(p.cate + vw * D + 4 * q);
+    if (item >= 0) rit = *reinterpret_cast<const f32x4*>(p.table + item * D + 4 * q);
+    x4 = *reinterpret_cast<const f32x4*>(p.cache + m * D + 4 * q);
+  }
+  const f32x4 x5 = *reinterpret_cast<const f32x4*>(p.hist + (size_t)u * D + 4 * q);
+  if (bad) atomicOr(p.err, 1);
+
+  // ---------------- SENET
+  const f32x4 xs[5] = {c1, c2, rit, x4, x5};
+  float z[6];
+  z[0] = 0.f;
+#pragma unroll
+  for (int f = 0; f < 5; ++f) z[f + 1] = group_sum<G>(xs[f][0] + xs[f][1] + xs[f][2] + xs[f][3]) / (float)D;
+  float qv[FBN_MAXR], a[6];
+  senet_excite<D>(z, p.w1, p.b1, p.w2, p.b2, p.R, qv, a);
+
+  // ---------------- stores
+  float* Vb = p.Vc ? p.Vc + (size_t)b * 5 * D + 4 * q : nullptr;
+  float* cb = (p.c && !p.c16) ? (float*)p.c + (size_t)b * p.ldc + 4 * q : nullptr;
+  short* cb16 = (p.c && p.c16) ? (short*)p.c + (size_t)b * p.ldc + 4 * q : nullptr;
+#pragma unroll
+  for (int f = 0; f < 5; ++f) {
+    const f32x4 v = xs[f] * a[f + 1];
+    if (p.Vc) *reinterpret_cast<f32x4*>(Vb + f * D) = v;
+    const bf16x4 v16 = (bf16x4){f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
+    if (cb16) *reinterpret_cast<bf16x4*>(cb16 + f * D) = v16;
+    else if (cb) *reinterpret_cast<f32x4*>(cb + f * D) = v;
+    if (p.Vc16) *reinterpret_cast<bf16x4*>(p.Vc16 + ((size_t)b * 5 + f) * D + 4 * q) = v16;
+  }
+  if (p.a_out) {
+#pragma unroll
+    for (int f = 0; f < 6; ++f)
+      if (f % G == q) p.a_out[(size_t)b * 6 + f] = a[f];   // G may be < 6 (D = 16)
+  }
+}
+
+// D/4 lanes per pair row, 64/(D/4) rows per wave.  LIST: a row's catalogue position comes from the
+// user's list (one 8-byte read per lane group, the same address in all its lanes), so the row indices
+// of a wave's 16-byte loads are per lane group instead of consecutive; everything after is the same.
+template <int D, bool LIST>
 __global__ void __launch_bounds__(256) rec_fields_kernel(RecFieldArgs p) {
   constexpr int G = D / 4, SPW = 64 / G;
   const int lane = threadIdx.x & 63, q = lane % G;
@@ -182,49 +244,53 @@ __global__ void __launch_bounds__(256) rec_fields_kernel(RecFieldArgs p) {
     const long long b = r0 + lane / G;            // pair row u * Mc + (m - m0)
     if (b >= P) continue;
     const int u = (int)(b / p.Mc);
-    const long long m = p.m0 + (b - (long long)u * p.Mc);
-    // ---------------- ids (validated as fbn_fields_fwd does: a bad id reads row 0 / a zero row)
-    long long item = p.item_id[m], lk = p.likes[m], vw = p.views[m];
-    bool bad = false;
-    if (lk < 0 || lk >= p.n_cate) { bad = true; lk = 0; }
-    if (vw < 0 || vw >= p.n_cate) { bad = true; vw = 0; }
-    if (item < 0 || item >= p.V) { bad = true; item = -1; }
-    const f32x4 c1 = *reinterpret_cast<const f32x4*>(p.cate + lk * D + 4 * q);
-    const f32x4 c2 = *reinterpret_cast<const f32x4*>(p.cate + vw * D + 4 * q);
-    f32x4 rit = {0.f, 0.f, 0.f, 0.f};
-    if (item >= 0) rit = *reinterpret_cast<const f32x4*>(p.table + item * D + 4 * q);
-    const f32x4 x4 = *reinterpret_cast<const f32x4*>(p.cache + m * D + 4 * q);
-    const f32x4 x5 = *reinterpret_cast<const f32x4*>(p.hist + (size_t)u * D + 4 * q);
-    if (bad) atomicOr(p.err, 1);
-
-    // ---------------- SENET
-    const f32x4 xs[5] = {c1, c2, rit, x4, x5};
-    float z[6];
-    z[0] = 0.f;
-#pragma unroll
-    for (int f = 0; f < 5; ++f) z[f + 1] = group_sum<G>(xs[f][0] + xs[f][1] + xs[f][2] + xs[f][3]) / (float)D;
-    float qv[FBN_MAXR], a[6];
-    senet_excite<D>(z, p.w1, p.b1, p.w2, p.b2, p.R, qv, a);
-
-    // ---------------- stores
-    float* Vb = p.Vc ? p.Vc + (size_t)b * 5 * D + 4 * q : nullptr;
-    float* cb = (p.c && !p.c16) ? (float*)p.c + (size_t)b * p.ldc + 4 * q : nullptr;
-    short* cb16 = (p.c && p.c16) ? (short*)p.c + (size_t)b * p.ldc + 4 * q : nullptr;
-#pragma unroll
-    for (int f = 0; f < 5; ++f) {
-      const f32x4 v = xs[f] * a[f + 1];
-      if (p.Vc) *reinterpret_cast<f32x4*>(Vb + f * D) = v;
-      const bf16x4 v16 = (bf16x4){f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
-      if (cb16) *reinterpret_cast<bf16x4*>(cb16 + f * D) = v16;
-      else if (cb) *reinterpret_cast<f32x4*>(cb + f * D) = v;
-      if (p.Vc16) *reinterpret_cast<bf16x4*>(p.Vc16 + ((size_t)b * 5 + f) * D + 4 * q) = v16;
+    long long m = p.m0 + (b - (long long)u * p.Mc);
+    if (LIST) {
+      m = p.cand_pos[(size_t)u * p.ldp + m];      // slot -> catalogue position
+      if (m >= p.M) { atomicOr(p.err, 1); m = -1; }
     }
-    if (p.a_out) {
-#pragma unroll
-      for (int f = 0; f < 6; ++f)
-        if (f % G == q) p.a_out[(size_t)b * 6 + f] = a[f];   // G may be < 6 (D = 16)
-    }
+    rec_pair_row<D, LIST>(p, u, m, b, q);
   }
+}
+
+// fbn_last_error() names the entry point the caller used, whichever of a shared check refused
+static void rec_err(const char* who, const char* what) {
+  char msg[192];
+  snprintf(msg, sizeof(msg), "%s: %s", who, what);
+  fbn_set_error(msg);
+}
+
+template <bool LIST>
+static int rec_fields_launch(const char* who, RecFieldArgs& a, int D, void* stream) {
+  if (!rec_dim_ok(D)) {
+    rec_err(who, "embedding_dim D must be one of 16,32,64,128,256");
+    return FBN_ERR_ARG;
+  }
+  if (a.R < 1 || a.R > FBN_MAXR || (a.ldc & 3) || a.m0 < 0) {
+    rec_err(who, LIST ? "need 1 <= R <= 8, ldc % 4 == 0, c0 >= 0" : "need 1 <= R <= 8, ldc % 4 == 0, m0 >= 0");
+    return FBN_ERR_ARG;
+  }
+  if (LIST && (a.M < 0 || (long long)a.ldp < (long long)a.m0 + a.Mc)) {
+    rec_err(who, "need M >= 0 and ldp >= c0 + Cc");
+    return FBN_ERR_ARG;
+  }
+  if (a.U <= 0 || a.Mc <= 0) return FBN_OK;
+  if ((long long)a.U * a.Mc > 0x7FFFFFFFll) {
+    rec_err(who, LIST ? "U * Cc pair rows must fit 31 bits (score in chunks)"
+                      : "U * Mc pair rows must fit 31 bits (score in chunks)");
+    return FBN_ERR_ARG;
+  }
+  const dim3 grid(rec_grid((long long)a.U * a.Mc, D)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  switch (D) {
+    case 16: fbn_launch(rec_fields_kernel<16, LIST>, grid, block, 0, st, a); break;
+    case 32: fbn_launch(rec_fields_kernel<32, LIST>, grid, block, 0, st, a); break;
+    case 64: fbn_launch(rec_fields_kernel<64, LIST>, grid, block, 0, st, a); break;
+    case 128: fbn_launch(rec_fields_kernel<128, LIST>, grid, block, 0, st, a); break;
+    default: fbn_launch(rec_fields_kernel<256, LIST>, grid, block, 0, st, a); break;
+  }
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
 }
 
 extern "C" int fbn_rec_fields(const int64_t* item_id, const int64_t* likes, const int64_t* views, const float* cache,
@@ -232,34 +298,26 @@ extern "C" int fbn_rec_fields(const int64_t* item_id, const int64_t* likes, cons
                               const float* w1, const float* b1, const float* w2, const float* b2, int R, float* Vc,
                               short* Vc16, void* c, int ldc, int c_bf16, float* a_out, int* err, int U, int m0, int Mc,
                               int D, void* stream) {
-  if (!rec_dim_ok(D)) {
-    fbn_set_error("fbn_rec_fields: embedding_dim D must be one of 16,32,64,128,256");
-    return FBN_ERR_ARG;
-  }
-  if (R < 1 || R > FBN_MAXR || (ldc & 3) || m0 < 0) {
-    fbn_set_error("fbn_rec_fields: need 1 <= R <= 8, ldc % 4 == 0, m0 >= 0");
-    return FBN_ERR_ARG;
-  }
-  if (U <= 0 || Mc <= 0) return FBN_OK;
-  if ((long long)U * Mc > 0x7FFFFFFFll) {
-    fbn_set_error("fbn_rec_fields: U * Mc pair rows must fit 31 bits (score in chunks)");
-    return FBN_ERR_ARG;
-  }
   RecFieldArgs a;
   a.item_id = item_id; a.likes = likes; a.views = views; a.cache = cache; a.hist = hist; a.cate = cate;
   a.table = table; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.Vc = Vc; a.Vc16 = Vc16; a.c = c; a.a_out = a_out;
   a.err = err; a.V = V; a.U = U; a.m0 = m0; a.Mc = Mc; a.ldc = ldc; a.R = R; a.n_cate = n_cate; a.c16 = c_bf16;
-  const dim3 grid(rec_grid((long long)U * Mc, D)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  switch (D) {
-    case 16: fbn_launch(rec_fields_kernel<16>, grid, block, 0, st, a); break;
-    case 32: fbn_launch(rec_fields_kernel<32>, grid, block, 0, st, a); break;
-    case 64: fbn_launch(rec_fields_kernel<64>, grid, block, 0, st, a); break;
-    case 128: fbn_launch(rec_fields_kernel<128>, grid, block, 0, st, a); break;
-    default: fbn_launch(rec_fields_kernel<256>, grid, block, 0, st, a); break;
-  }
-  FBN_CHECK_LAUNCH();
-  return FBN_OK;
+  a.cand_pos = nullptr; a.ldp = 0; a.M = 0;
+  return rec_fields_launch<false>("fbn_rec_fields", a, D, stream);
+}
+
+extern "C" int fbn_rec_fields_list(const int64_t* item_id, const int64_t* likes, const int64_t* views,
+                                   const float* cache, const float* hist, const float* cate, int n_cate,
+                                   const float* table, long long V, const float* w1, const float* b1, const float* w2,
+                                   const float* b2, int R, float* Vc, short* Vc16, void* c, int ldc, int c_bf16,
+                                   float* a_out, int* err, int U, const int64_t* cand_pos, int ldp, int c0, int Cc,
+                                   int M, int D, void* stream) {
+  RecFieldArgs a;
+  a.item_id = item_id; a.likes = likes; a.views = views; a.cache = cache; a.hist = hist; a.cate = cate;
+  a.table = table; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.Vc = Vc; a.Vc16 = Vc16; a.c = c; a.a_out = a_out;
+  a.err = err; a.V = V; a.U = U; a.m0 = c0; a.Mc = Cc; a.ldc = ldc; a.R = R; a.n_cate = n_cate; a.c16 = c_bf16;
+  a.cand_pos = cand_pos; a.ldp = ldp; a.M = M;
+  return rec_fields_launch<true>("fbn_rec_fields_list", a, D, stream);
 }
 
 // ------------------------------------------------------------------------------ top-K selection
@@ -280,6 +338,11 @@ struct RecTopkArgs {
   int64_t* out_index; int64_t* out_item; float* out_logit; float* out_prob;   // [U][K] (mode 1, optional)
   unsigned* status;
   int U, m0, Mc, L, exclude, K, nseg, mode;
+  // per-user lists (fbn_rec_topk_list; cand_pos null: the catalogue): column m0 + j of the chunk is slot
+  // m0 + j of cand_pos [U][ldp], the key's low word carries the slot, and out_slot [U][K] receives it
+  const int64_t* cand_pos;
+  int64_t* out_slot;
+  int ldp, M;
 };
 
 __device__ __forceinline__ unsigned long long rec_key(float x, unsigned pos, bool& nan) {
@@ -321,15 +384,22 @@ __global__ void __launch_bounds__(256) rec_topk_kernel(RecTopkArgs p) {
     if (i < n) {
       if (p.mode == 0) {
         const int j = base + i;
-        const long long m = (long long)p.m0 + j;
-        bool nan;
-        key = rec_key(p.logits[(size_t)u * p.Mc + j], (unsigned)m, nan);
-        if (nan) atomicOr(p.status, 1u);
-        if (p.exclude) {
-          const long long id = p.item_id[m];
-          bool ex = id == 0;
-          for (int l = 0; l < L; ++l) ex |= hist[l] != 0 && hist[l] == id;
-          if (ex) key = 0ull;
+        const long long col = (long long)p.m0 + j;      // the key's low word: position, or slot of a list
+        long long m = col;
+        if (p.cand_pos) {
+          m = p.cand_pos[(size_t)u * p.ldp + col];
+          if (m >= p.M) m = -1;
+        }
+        if (m >= 0) {                                   // an empty slot keeps key 0, whatever its logit holds
+          bool nan;
+          key = rec_key(p.logits[(size_t)u * p.Mc + j], (unsigned)col, nan);
+          if (nan) atomicOr(p.status, 1u);
+          if (p.exclude) {
+            const long long id = p.item_id[m];
+            bool ex = id == 0;
+            for (int l = 0; l < L; ++l) ex |= hist[l] != 0 && hist[l] == id;
+            if (ex) key = 0ull;
+          }
         }
       } else {
         key = i < K ? p.carry[(size_t)u * K + i] : p.ws[(size_t)u * p.nseg * K + (i - K)];
@@ -358,13 +428,20 @@ __global__ void __launch_bounds__(256) rec_topk_kernel(RecTopkArgs p) {
   const size_t o = (size_t)u * K + t;
   p.carry[o] = key;
   if (!p.out_index) return;
-  if (key == 0ull) {
+  const unsigned col = 0xFFFFFFFFu - (unsigned)key;
+  long long pos = col;
+  if (p.cand_pos && key != 0ull) {                     // a key only ever came from a live slot of this list;
+    pos = col < (unsigned)p.ldp ? p.cand_pos[(size_t)u * p.ldp + col] : -1;   // a foreign carry reads nothing
+    if (pos >= p.M) pos = -1;
+  }
+  if (key == 0ull || pos < 0) {
+    if (p.cand_pos) p.out_slot[o] = -1;
     p.out_index[o] = -1;
     p.out_item[o] = -1;
     p.out_logit[o] = -__builtin_inff();
     p.out_prob[o] = 0.f;
   } else {
-    const unsigned pos = 0xFFFFFFFFu - (unsigned)key;
+    if (p.cand_pos) p.out_slot[o] = (int64_t)col;
     const float x = rec_key_logit(key);
     p.out_index[o] = (int64_t)pos;
     p.out_item[o] = p.item_id[pos];
@@ -373,49 +450,46 @@ __global__ void __launch_bounds__(256) rec_topk_kernel(RecTopkArgs p) {
   }
 }
 
-static int rec_topk_check(int U, int Mc, int K) {
+static int rec_topk_check(const char* who, int U, int Mc, int K) {
   if (K < 1 || K > REC_KMAX) {
-    fbn_set_error("fbn_rec_topk: K must be in 1..256");
+    rec_err(who, "K must be in 1..256");
     return FBN_ERR_ARG;
   }
   if (U < 0 || Mc < 0) {
-    fbn_set_error("fbn_rec_topk: negative U or Mc");
+    rec_err(who, "negative U or Mc");
     return FBN_ERR_ARG;
   }
   return FBN_OK;
 }
 
 extern "C" size_t fbn_rec_topk_workspace_size(int U, int Mc, int K) {
-  if (rec_topk_check(U, Mc, K)) return 0;
+  if (rec_topk_check("fbn_rec_topk", U, Mc, K)) return 0;
   return (size_t)U * (size_t)fbn_cdiv(Mc, REC_SEG) * (size_t)K * sizeof(unsigned long long);
 }
 
-extern "C" int fbn_rec_topk(const float* logits, int U, int m0, int Mc, const int64_t* item_id,
-                            const int64_t* item_seq, int L, int exclude, int K, unsigned long long* carry, void* ws,
-                            size_t ws_bytes, int64_t* out_index, int64_t* out_item, float* out_logit, float* out_prob,
-                            unsigned* status, void* stream) {
-  if (int rc = rec_topk_check(U, Mc, K)) return rc;
+// the checks and the two launches of fbn_rec_topk / fbn_rec_topk_list (a: the pointers and list fields)
+static int rec_topk_run(const char* who, RecTopkArgs& a, int U, int m0, int Mc, int L, int exclude, int K,
+                        size_t ws_bytes, void* stream) {
+  if (int rc = rec_topk_check(who, U, Mc, K)) return rc;
   if (L < 0 || L > FBN_MAX_L) {
-    fbn_set_error("fbn_rec_topk: history length L must be in 0..32");
+    rec_err(who, "history length L must be in 0..32");
     return FBN_ERR_ARG;
   }
   if (m0 < 0 || (long long)U * Mc > 0x7FFFFFFFll || U > 65535) {
-    fbn_set_error("fbn_rec_topk: need m0 >= 0, U <= 65535 and U * Mc within 31 bits");
+    rec_err(who, "need m0 >= 0 (the first column of the chunk), U <= 65535 and U * Mc within 31 bits");
     return FBN_ERR_ARG;
   }
-  if (out_index && !(out_item && out_logit && out_prob)) {
-    fbn_set_error("fbn_rec_topk: the four outputs come together");
+  if (a.out_index && !(a.out_item && a.out_logit && a.out_prob)) {
+    rec_err(who, "the four outputs come together");
     return FBN_ERR_ARG;
   }
   if (ws_bytes < fbn_rec_topk_workspace_size(U, Mc, K)) {
-    fbn_set_error("fbn_rec_topk: workspace smaller than fbn_rec_topk_workspace_size(U, Mc, K)");
+    rec_err(who, "workspace smaller than fbn_rec_topk_workspace_size(U, Mc, K)");
     return FBN_ERR_ARG;
   }
   if (U == 0) return FBN_OK;
-  RecTopkArgs a;
-  a.logits = logits; a.item_id = item_id; a.item_seq = L > 0 ? item_seq : nullptr; a.carry = carry;
-  a.ws = (unsigned long long*)ws; a.out_index = out_index; a.out_item = out_item; a.out_logit = out_logit;
-  a.out_prob = out_prob; a.status = status; a.U = U; a.m0 = m0; a.Mc = Mc; a.L = L; a.exclude = exclude; a.K = K;
+  if (L <= 0) a.item_seq = nullptr;
+  a.U = U; a.m0 = m0; a.Mc = Mc; a.L = L; a.exclude = exclude; a.K = K;
   a.nseg = fbn_cdiv(Mc, REC_SEG);
   hipStream_t st = (hipStream_t)stream;
   if (a.nseg > 0) {
@@ -427,6 +501,37 @@ extern "C" int fbn_rec_topk(const float* logits, int U, int m0, int Mc, const in
   fbn_launch(rec_topk_kernel, dim3(1, U), dim3(256), 0, st, a);
   FBN_CHECK_LAUNCH();
   return FBN_OK;
+}
+
+extern "C" int fbn_rec_topk(const float* logits, int U, int m0, int Mc, const int64_t* item_id,
+                            const int64_t* item_seq, int L, int exclude, int K, unsigned long long* carry, void* ws,
+                            size_t ws_bytes, int64_t* out_index, int64_t* out_item, float* out_logit, float* out_prob,
+                            unsigned* status, void* stream) {
+  RecTopkArgs a;
+  a.logits = logits; a.item_id = item_id; a.item_seq = item_seq; a.carry = carry; a.ws = (unsigned long long*)ws;
+  a.out_index = out_index; a.out_item = out_item; a.out_logit = out_logit; a.out_prob = out_prob; a.status = status;
+  a.cand_pos = nullptr; a.out_slot = nullptr; a.ldp = 0; a.M = 0;
+  return rec_topk_run("fbn_rec_topk", a, U, m0, Mc, L, exclude, K, ws_bytes, stream);
+}
+
+extern "C" int fbn_rec_topk_list(const float* logits, int U, int c0, int Cc, const int64_t* cand_pos, int ldp, int M,
+                                 const int64_t* item_id, const int64_t* item_seq, int L, int exclude, int K,
+                                 unsigned long long* carry, void* ws, size_t ws_bytes, int64_t* out_slot,
+                                 int64_t* out_index, int64_t* out_item, float* out_logit, float* out_prob,
+                                 unsigned* status, void* stream) {
+  if (c0 < 0 || M < 0 || (long long)ldp < (long long)c0 + Cc) {
+    rec_err("fbn_rec_topk_list", "need c0 >= 0, M >= 0 and ldp >= c0 + Cc");
+    return FBN_ERR_ARG;
+  }
+  if ((out_index != nullptr) != (out_slot != nullptr)) {
+    rec_err("fbn_rec_topk_list", "the five outputs come together");
+    return FBN_ERR_ARG;
+  }
+  RecTopkArgs a;
+  a.logits = logits; a.item_id = item_id; a.item_seq = item_seq; a.carry = carry; a.ws = (unsigned long long*)ws;
+  a.out_index = out_index; a.out_item = out_item; a.out_logit = out_logit; a.out_prob = out_prob; a.status = status;
+  a.cand_pos = cand_pos; a.out_slot = out_slot; a.ldp = ldp; a.M = M;
+  return rec_topk_run("fbn_rec_topk_list", a, U, c0, Cc, L, exclude, K, ws_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------ rank of a held-out item
@@ -442,18 +547,31 @@ struct RecRankArgs {
   int* rank; int* n_eligible;  // [U]
   unsigned* status;
   int U, M, ld, L, exclude;
+  // per-user lists (fbn_rec_rank_list; cand_pos null: the catalogue, C == M): the C columns of logits are
+  // the slots of cand_pos [U][ldp], target_pos holds slots, and the key's low word is the slot
+  const int64_t* cand_pos;
+  int ldp, C;
 };
 
-// a target is ranked when it names a catalogue position whose item is not the padding item
-__device__ __forceinline__ bool rec_rank_valid(const RecRankArgs& p, long long t) {
-  return t >= 0 && t < p.M && p.item_id[t] != 0;
+// the catalogue position behind column j of user u's logits (0 <= j < C), or -1 for an empty slot
+__device__ __forceinline__ long long rec_rank_pos(const RecRankArgs& p, int u, long long j) {
+  if (!p.cand_pos) return j;
+  const long long m = p.cand_pos[(size_t)u * p.ldp + j];
+  return m < p.M ? m : -1;
+}
+
+// a target is ranked when it names a column with a catalogue position whose item is not the padding item
+__device__ __forceinline__ bool rec_rank_valid(const RecRankArgs& p, int u, long long t) {
+  if (t < 0 || t >= p.C) return false;
+  const long long m = rec_rank_pos(p, u, t);
+  return m >= 0 && p.item_id[m] != 0;
 }
 
 __global__ void __launch_bounds__(256) rec_rank_init_kernel(RecRankArgs p) {
   const int u = blockIdx.x * blockDim.x + threadIdx.x;
   if (u >= p.U) return;
   const long long t = p.target_pos[u];
-  const bool valid = rec_rank_valid(p, t);
+  const bool valid = rec_rank_valid(p, u, t);
   if (valid) {
     bool nan;
     rec_key(p.logits[(size_t)u * p.ld + t], (unsigned)t, nan);
@@ -470,11 +588,11 @@ __global__ void __launch_bounds__(256) rec_rank_kernel(RecRankArgs p) {
   __shared__ int cnt[4][2];
   const int t = threadIdx.x, u = blockIdx.y, seg = blockIdx.x;
   const int L = p.item_seq ? p.L : 0;
-  const int base = seg * REC_SEG, n = min(REC_SEG, p.M - base);
+  const int base = seg * REC_SEG, n = min(REC_SEG, p.C - base);
   const long long tp = p.target_pos[u];
   if (t < L) hist[t] = p.item_seq[(size_t)u * L + t];
   if (t == 0) {
-    const bool valid = rec_rank_valid(p, tp);
+    const bool valid = rec_rank_valid(p, u, tp);
     bool nan;
     tkey_s = valid ? rec_key(p.logits[(size_t)u * p.ld + tp], (unsigned)tp, nan) : 0ull;
     valid_s = valid;
@@ -487,16 +605,17 @@ __global__ void __launch_bounds__(256) rec_rank_kernel(RecRankArgs p) {
     const int i = i0 + t;
     bool e = false, g = false;
     if (i < n) {
-      const long long m = (long long)base + i;
-      e = true;
-      if (p.exclude) {
+      const long long j = (long long)base + i;            // column: catalogue position, or slot of a list
+      const long long m = rec_rank_pos(p, u, j);
+      e = m >= 0;                                          // an empty slot is never eligible
+      if (e && p.exclude) {
         const long long id = p.item_id[m];
         bool in_hist = false;
         for (int l = 0; l < L; ++l) in_hist |= hist[l] != 0 && hist[l] == id;
-        e = id != 0 && (m == tp || !in_hist);             // the target stays eligible inside its own history
+        e = id != 0 && (j == tp || !in_hist);             // the target stays eligible inside its own history
       }
       bool nan;
-      g = e && valid && m != tp && rec_key(p.logits[(size_t)u * p.ld + m], (unsigned)m, nan) > tkey;
+      g = e && valid && j != tp && rec_key(p.logits[(size_t)u * p.ld + j], (unsigned)j, nan) > tkey;
     }
     elig += __popcll(__ballot(e));
     above += __popcll(__ballot(g));
@@ -509,6 +628,19 @@ __global__ void __launch_bounds__(256) rec_rank_kernel(RecRankArgs p) {
     if (a) atomicAdd(p.rank + u, a);
     if (e) atomicAdd(p.n_eligible + u, e);
   }
+}
+
+// the two launches of fbn_rec_rank / fbn_rec_rank_list
+static int rec_rank_launch(const RecRankArgs& a, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  fbn_launch(rec_rank_init_kernel, dim3(fbn_cdiv(a.U, 256)), dim3(256), 0, st, a);
+  FBN_CHECK_LAUNCH();
+  const int nseg = fbn_cdiv(a.C, REC_SEG);
+  if (nseg > 0) {
+    fbn_launch(rec_rank_kernel, dim3(nseg, a.U), dim3(256), 0, st, a);
+    FBN_CHECK_LAUNCH();
+  }
+  return FBN_OK;
 }
 
 extern "C" int fbn_rec_rank(const float* logits, int ld, int U, int M, const int64_t* item_id,
@@ -526,16 +658,28 @@ extern "C" int fbn_rec_rank(const float* logits, int ld, int U, int M, const int
   RecRankArgs a;
   a.logits = logits; a.item_id = item_id; a.item_seq = L > 0 ? item_seq : nullptr; a.target_pos = target_pos;
   a.rank = rank; a.n_eligible = n_eligible; a.status = status; a.U = U; a.M = M; a.ld = ld; a.L = L;
-  a.exclude = exclude;
-  hipStream_t st = (hipStream_t)stream;
-  fbn_launch(rec_rank_init_kernel, dim3(fbn_cdiv(U, 256)), dim3(256), 0, st, a);
-  FBN_CHECK_LAUNCH();
-  const int nseg = fbn_cdiv(M, REC_SEG);
-  if (nseg > 0) {
-    fbn_launch(rec_rank_kernel, dim3(nseg, U), dim3(256), 0, st, a);
-    FBN_CHECK_LAUNCH();
+  a.exclude = exclude; a.cand_pos = nullptr; a.ldp = 0; a.C = M;
+  return rec_rank_launch(a, stream);
+}
+
+extern "C" int fbn_rec_rank_list(const float* logits, int ld, int U, int C, const int64_t* cand_pos, int ldp, int M,
+                                 const int64_t* item_id, const int64_t* item_seq, int L, int exclude,
+                                 const int64_t* target_slot, int* rank, int* n_eligible, unsigned* status,
+                                 void* stream) {
+  if (L < 0 || L > FBN_MAX_L) {
+    fbn_set_error("fbn_rec_rank_list: history length L must be in 0..32");
+    return FBN_ERR_ARG;
   }
-  return FBN_OK;
+  if (U < 0 || U > 65535 || C < 0 || ld < C || ldp < C || M < 0) {
+    fbn_set_error("fbn_rec_rank_list: need 0 <= U <= 65535, C >= 0, ld >= C, ldp >= C and M >= 0");
+    return FBN_ERR_ARG;
+  }
+  if (U == 0) return FBN_OK;
+  RecRankArgs a;
+  a.logits = logits; a.item_id = item_id; a.item_seq = L > 0 ? item_seq : nullptr; a.target_pos = target_slot;
+  a.rank = rank; a.n_eligible = n_eligible; a.status = status; a.U = U; a.M = M; a.ld = ld; a.L = L;
+  a.exclude = exclude; a.cand_pos = cand_pos; a.ldp = ldp; a.C = C;
+  return rec_rank_launch(a, stream);
 }
 
 // ------------------------------------------------------------------------------ rank record

@@ -15,6 +15,12 @@ reaches the host and the U x M matrix is never sorted.  ``rank`` counts, in the 
 eligible items lie above one held-out item per user (``fbn_rec_rank`` on one sweep's logits), and
 ``evaluate`` turns such ranks into HR / NDCG / MRR@K through ``rank_metrics.RankMetrics``.
 
+``score_lists`` / ``topk_lists`` / ``rank_lists`` do the same over a candidate list that is different
+for each user -- ``candidates [U, C]`` of item ids or catalogue positions, a negative entry an empty
+slot -- scoring only the listed pairs (``fbn_rec_fields_list`` reads the pair's catalogue position
+through the list; the selection and rank keys carry the slot, so ties go to the caller's own order),
+and ``evaluate_sampled`` ranks each held-out item against sampled negatives through them.
+
 Single device, bilinear "all"; a row-sharded table is out of scope.
 """
 from __future__ import annotations
@@ -40,6 +46,27 @@ def _state_of(state) -> Dict[str, torch.Tensor]:
             raise ValueError("Recommender serves one device: pass the assembled state_dict of a world > 1 trainer")
         return state.state_dict()
     raise TypeError(f"state must be a state_dict, a FiBiNETTrainer or the model module, not {type(state).__name__}")
+
+
+def _check_lists(item_seq, candidates, by: str, target_slot=None, k: Optional[int] = None):
+    """The argument checks of the ``*_lists`` methods, before anything is launched: -> (U, C).  Shapes
+    only, so it needs no device."""
+    if by not in ("item_id", "index"):
+        raise ValueError(f"by must be 'item_id' or 'index', not {by!r}")
+    if k is not None and not 1 <= int(k) <= K_MAX:
+        raise ValueError(f"k must be in 1..{K_MAX}")
+    if item_seq is not None and item_seq.dim() != 2:
+        raise ValueError("item_seq must be [U, L]")
+    U = 1 if item_seq is None else int(item_seq.shape[0])
+    if U < 1:
+        raise ValueError("item_seq holds no user")
+    if not isinstance(candidates, torch.Tensor) or candidates.dim() != 2 or candidates.is_floating_point():
+        raise ValueError("candidates must be an integer tensor [U, C]")
+    if int(candidates.shape[0]) != U or int(candidates.shape[1]) < 1:
+        raise ValueError(f"candidates is {tuple(candidates.shape)} for {U} users: need [U, C] with C >= 1")
+    if target_slot is not None and int(torch.as_tensor(target_slot).numel()) != U:
+        raise ValueError(f"target_slot holds {int(torch.as_tensor(target_slot).numel())} slots for {U} users")
+    return U, int(candidates.shape[1])
 
 
 class Recommender:
@@ -183,23 +210,30 @@ class Recommender:
              ptr(self.err), U, L, d, st)
         return seq if L else None, hist, U, L
 
-    def _chunks(self, U: int):
+    def _chunks(self, U: int, n: Optional[int] = None):
+        """(first column, columns) of the chunks over n columns: the catalogue (default), or a list's slots."""
+        n = self.M if n is None else n
         mc = max(1, self.chunk_rows // U)
-        for m0 in range(0, self.M, mc):
-            yield m0, min(mc, self.M - m0)
+        for m0 in range(0, n, mc):
+            yield m0, min(mc, n - m0)
 
-    def _forward_chunk(self, hist, U, m0, Mc) -> Dict:
+    def _forward_chunk(self, hist, U, m0, Mc, cand: Optional[torch.Tensor] = None) -> Dict:
         """The eval forward's activations of one chunk: a["logits"] / a["probs"] [U * Mc], row u * Mc + j
-        = user u, candidate m0 + j; the buffers are reused by the next chunk of the same size."""
+        = user u, candidate m0 + j -- catalogue position m0 + j, or with ``cand`` ([U, C] positions) slot
+        m0 + j of the user's own list; the buffers are reused by the next chunk of the same size."""
         p, c, dev = self.p, self.cat, self.device
+        if cand is None:
+            name, pairs = "fbn_rec_fields", (U, m0, Mc, self.d)
+        else:
+            name, pairs = "fbn_rec_fields_list", (U, ptr(cand), int(cand.shape[1]), m0, Mc, self.M, self.d)
 
         def fill(Vc, Vc16, cbuf, ldc, c_bf16, a_out, err, st):
-            call("fbn_rec_fields", ptr(c["item_id"]), ptr(c["likes_level"]), ptr(c["views_level"]), ptr(self.cache),
+            call(name, ptr(c["item_id"]), ptr(c["likes_level"]), ptr(c["views_level"]), ptr(self.cache),
                  ptr(hist), ptr(p["cate_emb.weight"]), int(p["cate_emb.weight"].shape[0]),
                  ptr(p["item_emb.weight"]), self.V, ptr(p["senet.excitation.0.weight"]),
                  ptr(p["senet.excitation.0.bias"]), ptr(p["senet.excitation.2.weight"]),
                  ptr(p["senet.excitation.2.bias"]), self.cfg.R, ptr(Vc), ptr(Vc16), ptr(cbuf), ldc, c_bf16,
-                 ptr(a_out), ptr(err), U, m0, Mc, self.d, st)
+                 ptr(a_out), ptr(err), *pairs, st)
 
         rows = U * Mc
         acts = self._acts.get(rows)
@@ -224,11 +258,13 @@ class Recommender:
             out = self._sweep(hist, U, logits)
         return out
 
-    def _sweep(self, hist, U: int, logits: bool) -> torch.Tensor:
-        """One catalogue sweep of the chunk loop collected into [U, M] (4 U M bytes)."""
-        out = torch.empty((U, self.M), dtype=torch.float32, device=self.device)
-        for m0, Mc in self._chunks(U):
-            a = self._forward_chunk(hist, U, m0, Mc)
+    def _sweep(self, hist, U: int, logits: bool, cand: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One sweep of the chunk loop collected into [U, M] (4 U M bytes) -- over the catalogue, or with
+        ``cand`` ([U, C] positions) over the slots of the users' lists into [U, C]."""
+        n = self.M if cand is None else int(cand.shape[1])
+        out = torch.empty((U, n), dtype=torch.float32, device=self.device)
+        for m0, Mc in self._chunks(U, n):
+            a = self._forward_chunk(hist, U, m0, Mc, cand)
             out[:, m0:m0 + Mc].copy_((a["logits"] if logits else a["probs"]).view(U, Mc))
         return out
 
@@ -334,5 +370,142 @@ class Recommender:
         if int(status.item()) & 1:
             raise ValueError("Recommender.evaluate: the logit of a ranked target is NaN")
         result = metrics.compute(ks)
+        self.check_ids()
+        return result
+
+    # ------------------------------------------------------------------ per-user candidate lists
+    def _lists(self, candidates: torch.Tensor, by: str) -> torch.Tensor:
+        """candidates [U, C] -> catalogue positions [U, C] (int64, contiguous, on the device); an id
+        the catalogue lacks becomes the empty slot -1."""
+        cand = candidates.to(self.device).long()
+        return (self.positions(cand) if by == "item_id" else cand).contiguous()
+
+    @torch.no_grad()
+    def score_lists(self, item_seq: Optional[torch.Tensor], candidates: torch.Tensor, *, by: str = "item_id",
+                    logits: bool = False) -> torch.Tensor:
+        """Probabilities (or logits) [U, C] of every user's own candidate list: ``candidates`` [U, C]
+        (int64) holds item ids (``by="item_id"``, mapped by :meth:`positions`) or catalogue positions
+        (``by="index"``).  A negative entry, or an id the catalogue lacks, is an empty slot and reads
+        probability 0 / logit -inf; a position >= M does too and sets the flag ``check_ids()`` raises
+        on.  ``item_seq=None`` with one row of candidates is the cold user.  Only the U x C pairs are
+        scored (chunked along the slots); nothing is copied to the host and nothing synchronises."""
+        U, _ = _check_lists(item_seq, candidates, by)
+        with torch.cuda.device(self.device):
+            st = _lib.stream_handle(self.device)
+            pos = self._lists(candidates, by)
+            _, hist, U, _ = self._hist(item_seq, st)
+            out = self._sweep(hist, U, logits, pos)
+            live = (pos >= 0) & (pos < self.M)
+            out = torch.where(live, out, torch.full_like(out, float("-inf") if logits else 0.0))
+        return out
+
+    @torch.no_grad()
+    def topk_lists(self, item_seq: Optional[torch.Tensor], candidates: torch.Tensor, k: int, *,
+                   exclude_history: bool = True, by: str = "item_id") -> Dict[str, torch.Tensor]:
+        """Each user's k best slots of its own list, best first: ``slot`` (index into the user's row of
+        ``candidates``), ``index`` (catalogue position), ``item_id``, ``logit``, ``prob``, all [U, k].
+        Equal logits go to the smaller slot -- the caller's own order -- and an item listed in two slots
+        is two candidates.  Empty slots are never returned; exclude_history as in :meth:`topk`.  With
+        fewer than k eligible slots the tail is slot -1, index -1, item_id -1, logit -inf, prob 0."""
+        U, C = _check_lists(item_seq, candidates, by, k=k)
+        k, dev = int(k), self.device
+        with torch.cuda.device(dev):
+            st = _lib.stream_handle(dev)
+            pos = self._lists(candidates, by)
+            seq, hist, U, L = self._hist(item_seq, st)
+            carry = torch.zeros((U, k), dtype=torch.int64, device=dev)
+            out = {n: torch.empty((U, k), dtype=torch.int64, device=dev) for n in ("slot", "index", "item_id")}
+            out.update({n: torch.empty((U, k), dtype=torch.float32, device=dev) for n in ("logit", "prob")})
+            chunks = list(self._chunks(U, C))
+            nws = int(_lib.lib().fbn_rec_topk_workspace_size(U, chunks[0][1], k))
+            ws = torch.empty(max(1, (nws + 7) // 8), dtype=torch.int64, device=dev)
+            for i, (c0, Cc) in enumerate(chunks):
+                a = self._forward_chunk(hist, U, c0, Cc, pos)
+                o = out if i == len(chunks) - 1 else {}
+                call("fbn_rec_topk_list", ptr(a["logits"]), U, c0, Cc, ptr(pos), C, self.M, ptr(self.cat["item_id"]),
+                     ptr(seq), L, int(bool(exclude_history)), k, ptr(carry), ptr(ws), nws, ptr(o.get("slot")),
+                     ptr(o.get("index")), ptr(o.get("item_id")), ptr(o.get("logit")), ptr(o.get("prob")),
+                     ptr(self.status), st)
+        return out
+
+    @torch.no_grad()
+    def rank_lists(self, item_seq: Optional[torch.Tensor], candidates: torch.Tensor, target_slot: torch.Tensor, *,
+                   exclude_history: bool = True, by: str = "item_id",
+                   _status: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """The rank of slot ``target_slot[u]`` among the eligible slots of user u's own list, in
+        ``topk_lists``' order: ``{"rank": int32 [U], "n_eligible": int32 [U]}``.  A slot is eligible when
+        it is not empty and, with exclude_history, passes :meth:`rank`'s id rule (the target's own slot
+        stays eligible when the history holds its item).  Rank 0 ("not ranked"): the target slot is
+        outside the list, empty, or holds the padding item.  One sweep of the lists into a [U, C] buffer
+        of logits, then one ``fbn_rec_rank_list`` call; no host copy and no sync."""
+        U, C = _check_lists(item_seq, candidates, by, target_slot=target_slot)
+        dev = self.device
+        with torch.cuda.device(dev):
+            st = _lib.stream_handle(dev)
+            pos = self._lists(candidates, by)
+            tslot = torch.as_tensor(target_slot).to(dev).long().reshape(-1).contiguous()
+            seq, hist, U, L = self._hist(item_seq, st)
+            buf = self._sweep(hist, U, True, pos)
+            out = {"rank": torch.empty(U, dtype=torch.int32, device=dev),
+                   "n_eligible": torch.empty(U, dtype=torch.int32, device=dev)}
+            call("fbn_rec_rank_list", ptr(buf), C, U, C, ptr(pos), C, self.M, ptr(self.cat["item_id"]), ptr(seq), L,
+                 int(bool(exclude_history)), ptr(tslot), ptr(out["rank"]), ptr(out["n_eligible"]),
+                 ptr(self.status if _status is None else _status), st)
+        return out
+
+    @torch.no_grad()
+    def evaluate_sampled(self, pairs, n_neg: int = 99, ks=(5, 10, 20), *, seed: int = 0,
+                         exclude_history: bool = True, max_users: Optional[int] = None,
+                         users_per_block: int = 1024) -> Dict:
+        """HR@K, NDCG@K and MRR@K with sampled negatives: the held-out item of every evaluation user is
+        ranked against ``n_neg`` catalogue positions instead of the whole catalogue.  ``pairs`` and the
+        selection of the positive rows are :meth:`evaluate`'s.  Per user the list is [target, n_neg
+        negatives], target_slot 0.  The negatives are drawn uniformly with replacement from [0, M) by a
+        device ``torch.Generator`` seeded with ``seed`` -- one ``torch.randint`` of [users, n_neg] per
+        block of at most ``users_per_block`` users, in order, so a result is reproducible for the same
+        pairs, seed and blocking.  A draw equal to the target's position becomes an empty slot; padding
+        items and (with exclude_history) history items among the draws are not eligible, by
+        :meth:`rank_lists`' rule, and a position drawn twice counts twice.  Returns
+        ``RankMetrics.compute(ks)`` plus ``"mean_candidates"``: the mean ``n_eligible`` over the ranked
+        users (0.0 without any).  Raises as :meth:`evaluate` does."""
+        from .rank_metrics import RankMetrics, _check_ks
+        ks = _check_ks(ks)
+        upb, n_neg = int(users_per_block), int(n_neg)
+        if upb < 1:
+            raise ValueError("users_per_block must be positive")
+        if n_neg < 0:
+            raise ValueError("n_neg must not be negative")
+        left = None if max_users is None else int(max_users)
+        dev = self.device
+        metrics = RankMetrics(dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)     # this evaluation's own NaN flag
+        n_cand = torch.zeros((), dtype=torch.int64, device=dev)    # sum of n_eligible over the ranked users
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+        for batch, labels in pairs:
+            if left is not None and left <= 0:
+                break
+            rows = (labels.to(dev).reshape(-1) == 1).nonzero().reshape(-1)      # the per-batch sync
+            if left is not None:
+                rows = rows[:left]
+                left -= int(rows.numel())
+            if rows.numel() == 0:
+                continue
+            seq, tgt = batch["item_seq"].to(dev)[rows], batch["item_id"].to(dev).reshape(-1)[rows]
+            for r0 in range(0, int(rows.numel()), upb):
+                tpos = self.positions(tgt[r0:r0 + upb])
+                n = int(tpos.numel())
+                neg = torch.randint(0, self.M, (n, n_neg), generator=gen, device=dev, dtype=torch.int64)
+                neg = torch.where(neg == tpos[:, None], torch.full_like(neg, -1), neg)
+                cand = torch.cat([tpos[:, None], neg], dim=1)
+                out = self.rank_lists(seq[r0:r0 + upb], cand, torch.zeros(n, dtype=torch.int64, device=dev),
+                                      exclude_history=exclude_history, by="index", _status=status)
+                metrics.update(out["rank"])
+                n_cand += torch.where(out["rank"] > 0, out["n_eligible"], torch.zeros_like(out["n_eligible"])).sum()
+        self.status |= status
+        if int(status.item()) & 1:
+            raise ValueError("Recommender.evaluate_sampled: the logit of a ranked target is NaN")
+        result = metrics.compute(ks)
+        result["mean_candidates"] = float(n_cand.item()) / result["n"] if result["n"] else 0.0
         self.check_ids()
         return result

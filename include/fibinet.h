@@ -740,6 +740,56 @@ int fbn_rec_rank(const float* logits, int ld, int U, int M, const int64_t* item_
 #define FBN_RANK_REC_WORDS 260
 int fbn_rank_hist(const int* rank, long long n, unsigned long long* rec, void* stream);
 
+/* ---------------------------------------------------------------- serving: per-user candidate lists
+ * The same scoring loop (src/Prediction.py:106-113) when every user has a shortlist of its own instead of
+ * the shared catalogue: cand_pos [U][ldp] (int64) holds catalogue positions, slot j is the index into a
+ * user's list, and a negative entry is an EMPTY SLOT (ragged lists, filtered candidates).  A position
+ * >= M is treated as an empty slot everywhere.  A position that occurs in two slots of a user is two
+ * candidates: both are scored, both may be returned, and each counts in a rank.
+ *
+ * fbn_rec_fields_list: fbn_rec_fields with the pair (u, m) addressed through the list -- pair row
+ * p = u * Cc + (j - c0) for the slots j in [c0, c0 + Cc), m = cand_pos[u * ldp + j] -- replacing the same
+ * reference lines over per-user rows.  A non-empty slot runs the device functions of fbn_rec_fields in the
+ * same order, so its outputs are the bits fbn_rec_fields writes for (u, m).  An empty slot reads no table
+ * and no cache: X1..X4 = 0, X5 = hist[u], and SENET and every requested output are still written, so each
+ * row handed to the GEMMs is defined; it sets no flag.  m >= M is treated as empty and sets bit 0 of the
+ * sticky *err (the IndexError path; nothing faults).  D, R, ldc as fbn_rec_fields; c0 >= 0, ldp >= c0 + Cc,
+ * M >= 0, U * Cc < 2^31 (else FBN_ERR_ARG, checked on the host before any device work); U <= 0 or
+ * Cc <= 0 launches nothing. */
+int fbn_rec_fields_list(const int64_t* item_id, const int64_t* likes, const int64_t* views, const float* cache,
+                        const float* hist, const float* cate, int n_cate, const float* table, long long V,
+                        const float* w1, const float* b1, const float* w2, const float* b2, int R, float* Vc,
+                        short* Vc16, void* c, int ldc, int c_bf16, float* a_out, int* err, int U,
+                        const int64_t* cand_pos, int ldp, int c0, int Cc, int M, int D, void* stream);
+/* fbn_rec_topk_list: fbn_rec_topk over the chunk's logits [U][Cc] of the slots [c0, c0 + Cc) of cand_pos
+ * [U][ldp]; replaces a host-side sort of each user's list.  key = {order-preserving image of the f32
+ * logit, 0xFFFFFFFF - slot}: equal logits go to the smaller slot -- the caller's own order -- and a
+ * position held by two slots is two candidates with two keys.  An empty slot or a position >= M takes
+ * the "no candidate" key 0 before the NaN test, so whatever its logit holds never sets *status; a NaN in
+ * a live slot ranks below every number and sets bit 0.  exclude != 0: fbn_rec_topk's rule on
+ * item_id[cand_pos[u][j]].  Outputs (optional, together) [U][K], best first: slot, catalogue position,
+ * its item_id, logit, sigmoid(logit); with fewer than K eligible slots the tail is slot -1, position -1,
+ * item_id -1, logit -inf, probability 0.  Carry, workspace (fbn_rec_topk_workspace_size(U, Cc, K)), the
+ * K range and the two launches are fbn_rec_topk's; c0 >= 0, ldp >= c0 + Cc, M >= 0 (else FBN_ERR_ARG). */
+int fbn_rec_topk_list(const float* logits, int U, int c0, int Cc, const int64_t* cand_pos, int ldp, int M,
+                      const int64_t* item_id, const int64_t* item_seq, int L, int exclude, int K,
+                      unsigned long long* carry, void* ws, size_t ws_bytes, int64_t* out_slot, int64_t* out_index,
+                      int64_t* out_item, float* out_logit, float* out_prob, unsigned* status, void* stream);
+/* fbn_rec_rank_list: fbn_rec_rank over a user's list: logits [U][ld] whose columns 0 .. C-1 (C <= ld) are
+ * the slots of cand_pos [U][ldp] (ldp >= C), and t = target_slot[u]; replaces ranking the list's scores
+ * on the host.  Keys are fbn_rec_topk_list's slot keys.
+ *   rank[u]       = 1 + #{j != t : eligible(u, j) and key(j) > key(t)}
+ *   n_eligible[u] = #{j : eligible(u, j)}
+ * eligible(u, j): the slot is non-empty and its position m is < M; with exclude != 0 additionally
+ * fbn_rec_rank's id rule on item_id[m], where the target's own slot stays eligible when its id is in the
+ * history (a second slot holding the same position does not).  rank[u] = 0 when t is outside [0, C),
+ * names an empty slot (or a position >= M) or names the padding item; n_eligible[u] is still the count.
+ * Bit 0 of *status: a NaN logit at a ranked target, nowhere else.  The U limit, the two launches and the
+ * integer atomics are fbn_rec_rank's; 0 <= L <= 32, ld >= C >= 0, ldp >= C, M >= 0 (else FBN_ERR_ARG). */
+int fbn_rec_rank_list(const float* logits, int ld, int U, int C, const int64_t* cand_pos, int ldp, int M,
+                      const int64_t* item_id, const int64_t* item_seq, int L, int exclude,
+                      const int64_t* target_slot, int* rank, int* n_eligible, unsigned* status, void* stream);
+
 /* ---------------------------------------------------------------- step programs (native step driver)
  * Replaces the Python loop body that issues one training step (src/train_fibinet.py:113-123): the
  * host records a step's calls of this library -- entry point, arguments, and the cross-stream

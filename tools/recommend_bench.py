@@ -18,6 +18,14 @@ library's kernel probes; "forward" is the whole chunk forward, fields included).
                     fbn_rec_rank, fbn_rank_hist
   (b) topk_ms       Recommender.topk(k = 10) of the same users
 with (a)'s kernel spans per stage; written to profiles/recommend_rank_eval.json.
+
+--lists: per-user shortlists, U = 64 users, C = 500 slots each (5 % empty), K = 10,
+d = 128, once in fp32 and once in bf16:
+  (a) topk_lists_ms  Recommender.topk_lists over the U x C pairs
+  (b) topk_ms        Recommender.topk of the same users over the whole catalogue (U x M pairs)
+per call, the two routes interleaved after a warm-up; a run times several back-to-back calls with one
+HIP event pair so the window is not a single short call.  No threshold: the two figures and their
+ratio, written to profiles/recommend_lists.json.
 """
 import argparse
 import json
@@ -132,6 +140,72 @@ def rank_eval(args, rec, seq, target):
     print(json.dumps(res))
 
 
+def _catalogue(M, g):
+    x = torch.randn((M, 128), generator=g)
+    return {"item_id": torch.arange(M), "likes_level": torch.randint(0, 11, (M,), generator=g),
+            "views_level": torch.randint(0, 11, (M,), generator=g), "item_emb_d128": x / x.norm(dim=1, keepdim=True)}
+
+
+def lists_bench(args):
+    """--lists: topk_lists over per-user shortlists beside the full-catalogue topk of the same users."""
+    dev = torch.device("cuda", 0)
+    U, M, C, K, d, L = args.users, args.items, args.slots, args.k, args.d, 20
+    res = {"device": torch.cuda.get_device_name(dev), "users": U, "items": M, "slots": C, "k": K, "d": d,
+           "runs": args.runs, "statistic": "median of runs; each run times `calls` back-to-back calls with one "
+                                           "HIP event pair and divides by `calls`; the two routes interleaved",
+           "modes": {}}
+    for dtype in ("fp32", "bf16"):
+        cfg = {"embedding_dim": d, "vocab_size": M, "compute_dtype": dtype}
+        torch.manual_seed(3)
+        model = build_model(None, cfg).eval()
+        g = torch.Generator().manual_seed(5)
+        cat = _catalogue(M, g)
+        seq = torch.randint(1, M, (U, L), generator=g)
+        seq[torch.rand((U, L), generator=g) < 0.3] = 0
+        cand = torch.randint(0, M, (U, C), generator=g)
+        cand[torch.rand((U, C), generator=g) < 0.05] = -1          # ragged lists: 5 % empty slots
+        seq, cand = seq.to(dev), cand.to(dev)
+        rec = Recommender(model.state_dict(), cfg, cat, device=dev, chunk_rows=args.chunk_rows)
+        calls = {"lists": args.list_calls, "catalogue": 2}
+
+        def lists():
+            for _ in range(calls["lists"]):
+                out = rec.topk_lists(seq, cand, K, by="index")
+            return out
+
+        def catalogue():
+            for _ in range(calls["catalogue"]):
+                out = rec.topk(seq, K)
+            return out
+
+        lists(), catalogue()                                    # warm-up (allocations, bf16 images, both shapes)
+        ta, tb = [], []
+        for _ in range(args.runs):                              # interleaved A/B
+            t, la = _timed(lists)
+            ta.append(t / calls["lists"])
+            t, lb = _timed(catalogue)
+            tb.append(t / calls["catalogue"])
+        rec.check_ids()
+        # the shortlist's winners come from the catalogue's scores: every returned logit is that pair's
+        full = rec.score(seq, logits=True)
+        live = la["index"] >= 0
+        same = (full.gather(1, la["index"].clamp(min=0)) - la["logit"])[live].abs().max().item()
+        ma, mb = statistics.median(ta), statistics.median(tb)
+        res["modes"][dtype] = {
+            "chunk_rows": rec.chunk_rows, "list_chunks": len(list(rec._chunks(U, C))),
+            "catalogue_chunks": len(list(rec._chunks(U))), "calls_per_run": dict(calls),
+            "topk_lists_ms": round(ma, 4), "topk_ms": round(mb, 4), "ratio_topk_over_topk_lists": round(mb / ma, 2),
+            "topk_lists_ms_min_max": [round(min(ta), 4), round(max(ta), 4)],
+            "topk_ms_min_max": [round(min(tb), 4), round(max(tb), 4)],
+            "pairs_scored": {"lists": U * C, "catalogue": U * M},
+            "max_abs_dlogit_vs_catalogue_scores": same}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--users", type=int, default=64)
@@ -143,11 +217,16 @@ def main():
     ap.add_argument("--chunk-rows", type=int, default=None)
     ap.add_argument("--runs", type=int, default=RUNS)
     ap.add_argument("--rank-eval", action="store_true", help="time rank() + RankMetrics.update against topk")
+    ap.add_argument("--lists", action="store_true", help="time topk_lists on per-user shortlists against topk")
+    ap.add_argument("--slots", type=int, default=500, help="--lists: slots per user")
+    ap.add_argument("--list-calls", type=int, default=20, help="--lists: topk_lists calls per timed run")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join("profiles", "recommend_rank_eval.json" if args.rank_eval
-                                else "recommend_vs_expanded.json")
+        args.out = os.path.join("profiles", "recommend_lists.json" if args.lists else
+                                "recommend_rank_eval.json" if args.rank_eval else "recommend_vs_expanded.json")
+    if args.lists:
+        return lists_bench(args)
     dev = torch.device("cuda", 0)
     U, M, K, d, L, B = args.users, args.items, args.k, args.d, 20, args.batch
     cfg = {"embedding_dim": d, "vocab_size": M, "compute_dtype": args.dtype}
