@@ -794,9 +794,14 @@ extern "C" int fbn_adam_selftest(int n, unsigned seed, unsigned long long* dev, 
 // F+1 steps and its clip coefficient in coef_hist, and the next replay of the row applies step
 // last[r] with that gradient before the zero-gradient steps (same operations, same order: still
 // bit-identical to eager Adam), so a touched row is read and written once per visit instead of
-// twice.  fbn_adam_flush brings the whole table up to date (checkpoint, evaluation).  The schedule
-// constants of the last W <= FBN_LAZY_MAX_LAG steps sit in LDS.
-#define FBN_LAZY_MAX_LAG 512
+// twice.  fbn_adam_flush brings the whole table up to date (checkpoint, evaluation).
+// ONE replay engine does the per-row arithmetic of all of them (replay_sorted: adam_tabk on four
+// wave-wide rows at a time at D >= 128, on one row per lane group below).  Every kernel is a front
+// end that decides which rows its lanes take (take_row: last and pend updated there) and hands the
+// wave's rows to the engine: the step's claims (adam_claim2), the claimed rows of the host-split
+// exchange (adam_catchup), the rolling window and the flush (adam_window2), the prefetches
+// (adam_pretag + adam_prefetch2, the one-pass adam_prefetch, adam_pfbin + adam_pfreplay).
+#define FBN_LAZY_MAX_LAG 512   // the largest window F
 
 // Row state: ONE 16-B record per table row, {u64 pre-claim tag, i32 last, i32 pend}, so a claim
 // that needs all three (the critical-path adam_claim2, the prefetch) pulls one sector per row
@@ -822,7 +827,7 @@ struct PendSrc {
 static inline PendSrc make_pend(int* pend, const float* ring, const float* coef_hist, long long stride, int ring_n) {
   return PendSrc{pend, ring, coef_hist, stride, ring_n & ~FBN_RING_BF16, (ring_n & FBN_RING_BF16) ? 1 : 0};
 }
-// N ring elements at element offset go (f32, or bf16 widened).  Branch-free, as row_load needs (a load
+// N ring elements at element offset go (f32, or bf16 widened).  Branch-free, as pend_load needs (a load
 // under a branch makes hipcc drain every load in flight at the next use): ONE load of N floats' bytes
 // from the f32 address or the bf16 one -- a bf16 ring reads N bf16 values plus N more it ignores (the
 // trainer pads a bf16 ring by 16 elements so the last row's wider read stays inside the allocation) --
@@ -840,106 +845,51 @@ __device__ __forceinline__ V ring_load(const float* ring, int bf16, size_t go) {
   }
   return x;
 }
-
-template <int D, bool DW>
-__device__ __forceinline__ void replay_rows(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
-                                            long long r, int q, int k0, int t, const AdamConsts* __restrict__ win,
-                                            int w0, const AdamConsts* __restrict__ table, float wd, float b2,
-                                            float omb2, float eps, const PendSrc& ps) {
-  const size_t off = (size_t)r * D + 4 * q;
-  f32x4 pp = *reinterpret_cast<f32x4*>(p + off);
-  f32x4 mm = *reinterpret_cast<f32x4*>(m + off);
-  f32x4 vv = *reinterpret_cast<f32x4*>(v + off);
-  int s = k0;
-  if (ps.pend) {
-    const int pe = ps.pend[(size_t)(r) * FBN_RS_I];
-    if (pe >= 0) {   // step k0 with the deferred gradient (what fbn_adam_touched would have applied)
-      const f32x4 gg = ring_load<f32x4, 4>(ps.ring, ps.bf16, (size_t)(k0 % ps.ring_n) * ps.ring_stride +
-                                                                 (size_t)pe * D + 4 * q);
-      const float coef = ps.coef_hist[k0];
-      const AdamConsts k = k0 >= w0 ? win[k0 - w0] : table[k0];
-      adam_tab4<DW>(pp, mm, vv, gg * coef, wd, b2, omb2, eps, k);
-      s = k0 + 1;
-    }
-  }
-  // the rolling window keeps every row within F steps, so the constants of steps k0 .. t-1 sit in
-  // the LDS window [w0, t); steps before w0 (a row the window has not reached: only if F changed)
-  // read the global table in a loop of their own, so the hot loop's reads stay ds_read
-  for (; s < t && s < w0; ++s) adam_zero_tab4<DW>(pp, mm, vv, wd, b2, omb2, eps, table[s]);
-  for (; s < t; ++s) {
-    const AdamConsts k = win[s - w0];
-    adam_zero_tab4<DW>(pp, mm, vv, wd, b2, omb2, eps, k);
-  }
-  *reinterpret_cast<f32x4*>(p + off) = pp;
-  *reinterpret_cast<f32x4*>(m + off) = mm;
-  *reinterpret_cast<f32x4*>(v + off) = vv;
-}
-
-// One row's replay split into its loads and its arithmetic, so a wave can issue the next round's
-// loads before it computes the current round (adam_catchup_kernel).  pe = pend[r] (read with
-// last[r] while scanning).
-struct RowRegs {
-  f32x4 p, m, v, g;
-  float c;
-  AdamConsts k;   // step k0's constants (the deferred-gradient step), read with the row
-};
-template <int D>
-__device__ __forceinline__ void row_load(RowRegs& x, const float* __restrict__ p, const float* __restrict__ m,
-                                         const float* __restrict__ v, int r, int q, int k0, int pe,
-                                         const PendSrc& ps, const AdamConsts* __restrict__ table) {
-  const size_t off = (size_t)r * D + 4 * q;
-  x.p = *reinterpret_cast<const f32x4*>(p + off);
-  x.m = *reinterpret_cast<const f32x4*>(m + off);
-  x.v = *reinterpret_cast<const f32x4*>(v + off);
-  // branch-free (a load under a branch makes hipcc wait vmcnt(0) at the next use of any load,
-  // which would drain the next round's loads): no deferred gradient -> an L2-resident dummy line
+// A row's deferred gradient -- the N elements from element `col` of vector pe in the ring slot of step
+// k0 -- and that step's clip coefficient.  Branch-free (a load under a branch makes hipcc wait
+// vmcnt(0) at the next use of any load, which would drain the next rows' loads in flight): a row with
+// no deferred gradient (pe < 0) reads an L2-resident dummy line, the head of p.
+template <typename V, int N, int D>
+__device__ __forceinline__ void pend_load(V& g, float& c, const PendSrc& ps, const float* __restrict__ p, int k0,
+                                          int pe, int col) {
   const float* ring = ps.ring ? ps.ring : p;
   const float* coef = ps.coef_hist ? ps.coef_hist : p;
   const size_t go = pe >= 0 ? (size_t)(k0 % ps.ring_n) * ps.ring_stride + (size_t)pe * D : 0;
-  x.g = ring_load<f32x4, 4>(ring, ps.bf16, go + 4 * q);
-  x.c = coef[pe >= 0 ? k0 : 0];
-  x.k = table[k0];
-}
-template <int D, bool DW>
-__device__ __forceinline__ void row_replay_store(RowRegs& x, float* __restrict__ p, float* __restrict__ m,
-                                                 float* __restrict__ v, int r, int q, int k0, bool deferred, int t,
-                                                 const AdamConsts* __restrict__ win, int w0,
-                                                 const AdamConsts* __restrict__ table, float wd, float b2, float omb2,
-                                                 float eps) {
-  int s = k0;
-  if (deferred) {   // step k0 with the deferred gradient (what fbn_adam_touched would have applied)
-    adam_tab4<DW>(x.p, x.m, x.v, x.g * x.c, wd, b2, omb2, eps, x.k);
-    s = k0 + 1;
-  }
-  for (; s < t && s < w0; ++s) adam_zero_tab4<DW>(x.p, x.m, x.v, wd, b2, omb2, eps, table[s]);
-  for (; s < t; ++s) {
-    const AdamConsts k = win[s - w0];
-    adam_zero_tab4<DW>(x.p, x.m, x.v, wd, b2, omb2, eps, k);
-  }
-  const size_t off = (size_t)r * D + 4 * q;
-  *reinterpret_cast<f32x4*>(p + off) = x.p;
-  *reinterpret_cast<f32x4*>(m + off) = x.m;
-  *reinterpret_cast<f32x4*>(v + off) = x.v;
+  g = ring_load<V, N>(ring, ps.bf16, go + col);
+  c = coef[pe >= 0 ? k0 : 0];
 }
 
-// D >= 128: one row per round, 64 lanes x D/64 elements.  The row, its replay start k0 and its
-// deferred vector are wave-uniform, so the step loop is scalar and each step's constants arrive by
-// scalar loads (no LDS window, no sort, no lane groups waiting on a longer neighbour row).
+// This lane takes row rr (row state rs, behind step T) for the replay: r = the row, pe = its deferred
+// vector, key = its first zero-gradient step (after the deferred one); the row is marked up to date.
+__device__ __forceinline__ void take_row(int& r, int& key, int& pe, long long rr, const int4& rs, int T,
+                                         int* __restrict__ last, const PendSrc& ps) {
+  r = (int)rr;
+  if (ps.pend) pe = rs.w;
+  key = rs.z + (pe >= 0 ? 1 : 0);
+  last[(size_t)(rr) * FBN_RS_I] = T;
+  if (pe >= 0) ps.pend[(size_t)(rr) * FBN_RS_I] = -1;
+}
+
+// A wave's rows, one per lane (row r, key, deferred vector pe), sorted by key ascending: a bitonic
+// network over lane shuffles.  (A macro: as an inline function taking the three by reference the
+// engines compiled to other code than with the network written in place; this and the two helpers
+// written out below are recorded in profiles/r09_one_engine_asm_compare.txt.)
+#define FBN_SORT_ROWS(r, key, pe, lane)                                                                          \
+  _Pragma("unroll") for (int kk = 2; kk <= 64; kk <<= 1)                                                         \
+    _Pragma("unroll") for (int j = kk >> 1; j > 0; j >>= 1) {                                                    \
+      const int ok = __shfl_xor(key, j, 64), orr = __shfl_xor(r, j, 64), ope = __shfl_xor(pe, j, 64);            \
+      const bool up = (lane & kk) == 0, lower = (lane & j) == 0;                                                 \
+      if (lower == up ? ok < key : ok > key) {                                                                   \
+        key = ok;                                                                                                \
+        r = orr;                                                                                                 \
+        pe = ope;                                                                                                \
+      }                                                                                                          \
+    }
+
+// A wave-wide row (D >= 128): 64 lanes x D/64 elements.
 template <int N> struct FVec;
 template <> struct FVec<2> { typedef float T __attribute__((ext_vector_type(2))); };
 template <> struct FVec<4> { typedef f32x4 T; };
-template <bool DW, int N>
-__device__ __forceinline__ void adam_tabv(typename FVec<N>::T& pp, typename FVec<N>::T& mm, typename FVec<N>::T& vv,
-                                          typename FVec<N>::T gg, float wd, float b2, float omb2, float eps,
-                                          const AdamConsts& k) {
-#pragma unroll
-  for (int e = 0; e < N; ++e) {
-    float me = mm[e], ve = vv[e];
-    pp[e] = adam_tab1<DW>(pp[e], me, ve, gg[e], wd, b2, omb2, eps, k);
-    mm[e] = me;
-    vv[e] = ve;
-  }
-}
 template <int D>
 struct WideRow {
   static constexpr int N = D / 64;
@@ -957,34 +907,7 @@ __device__ __forceinline__ void wide_load(WideRow<D>& x, const float* __restrict
   x.p = *reinterpret_cast<const V*>(p + off);
   x.m = *reinterpret_cast<const V*>(m + off);
   x.v = *reinterpret_cast<const V*>(v + off);
-  const float* ring = ps.ring ? ps.ring : p;   // branch-free, as row_load
-  const float* coef = ps.coef_hist ? ps.coef_hist : p;
-  const size_t go = pe >= 0 ? (size_t)(k0 % ps.ring_n) * ps.ring_stride + (size_t)pe * D : 0;
-  x.g = ring_load<V, N>(ring, ps.bf16, go + lane * N);
-  x.c = coef[pe >= 0 ? k0 : 0];
-}
-// rows a and b (k0a <= k0b after the sort): deferred-gradient steps, then the steps both still
-// need side by side, then the longer row's remaining steps alone (all loop bounds wave-uniform)
-template <int D, bool DW>
-__device__ __forceinline__ void wide_replay_pair(WideRow<D>& a, int ka, int pa, WideRow<D>& b, int kb, int pb, int t,
-                                                 const AdamConsts* __restrict__ table, float wd, float b2,
-                                                 float omb2, float eps) {
-  typedef typename WideRow<D>::V V;
-  constexpr int N = WideRow<D>::N;
-  if (pa >= 0) adam_tabv<DW, N>(a.p, a.m, a.v, a.g * a.c, wd, b2, omb2, eps, table[ka]);
-  if (pb >= 0) adam_tabv<DW, N>(b.p, b.m, b.v, b.g * b.c, wd, b2, omb2, eps, table[kb]);
-  int sa = ka + (pa >= 0 ? 1 : 0), sb = kb + (pb >= 0 ? 1 : 0);
-  const V zero = {};
-  const int both = min(t - sa, t - sb);
-  for (int i = 0; i < both; ++i) {
-    const AdamConsts k1 = table[sa + i], k2 = table[sb + i];
-    adam_tabv<DW, N>(a.p, a.m, a.v, zero, wd, b2, omb2, eps, k1);
-    adam_tabv<DW, N>(b.p, b.m, b.v, zero, wd, b2, omb2, eps, k2);
-  }
-  sa += both > 0 ? both : 0;
-  sb += both > 0 ? both : 0;
-  for (; sa < t; ++sa) adam_tabv<DW, N>(a.p, a.m, a.v, zero, wd, b2, omb2, eps, table[sa]);
-  for (; sb < t; ++sb) adam_tabv<DW, N>(b.p, b.m, b.v, zero, wd, b2, omb2, eps, table[sb]);
+  pend_load<V, N, D>(x.g, x.c, ps, p, k0, pe, lane * N);
 }
 template <int D>
 __device__ __forceinline__ void wide_store(const WideRow<D>& x, float* __restrict__ p, float* __restrict__ m,
@@ -994,49 +917,6 @@ __device__ __forceinline__ void wide_store(const WideRow<D>& x, float* __restric
   *reinterpret_cast<V*>(p + off) = x.p;
   *reinterpret_cast<V*>(m + off) = x.m;
   *reinterpret_cast<V*>(v + off) = x.v;
-}
-
-// A wave's cnt rows (lanes 0..cnt-1 hold row r, replay start key, deferred vector pe; sorted by
-// key), brought to T steps two at a time: consecutive rows of the sorted order (similar replay
-// lengths) share the step loop -- four independent update chains per lane -- and the next pair's
-// loads are in flight meanwhile.  Slots past cnt: row 0 with no steps, not stored.
-template <int D, bool DW>
-__device__ __forceinline__ void wide_rows(int r, int key, int pe, int cnt, int T, float* __restrict__ p,
-                                          float* __restrict__ m, float* __restrict__ v, int* __restrict__ last,
-                                          const AdamConsts* __restrict__ table, float wd, float b2, float omb2,
-                                          float eps, const PendSrc& ps, int lane) {
-  auto get = [&](int idx, int& rr, int& kk, int& pp) {   // idx wave-uniform
-    const int sl = idx < cnt ? idx : 0;
-    rr = __builtin_amdgcn_readlane(r, sl);
-    kk = __builtin_amdgcn_readlane(key, sl);
-    pp = __builtin_amdgcn_readlane(pe, sl);
-    if (idx >= cnt) { rr = 0; kk = T; pp = -1; }
-  };
-  int ra, ka, pa, rb, kb, pb;
-  get(0, ra, ka, pa);
-  get(1, rb, kb, pb);
-  WideRow<D> xa, xb;
-  wide_load<D>(xa, p, m, v, ra, ka, pa, ps, lane);
-  wide_load<D>(xb, p, m, v, rb, kb, pb, ps, lane);
-  for (int j0 = 0; j0 < cnt; j0 += 2) {
-    int rna, kna, pna, rnb, knb, pnb;
-    get(j0 + 2, rna, kna, pna);
-    get(j0 + 3, rnb, knb, pnb);
-    WideRow<D> na, nb;
-    wide_load<D>(na, p, m, v, rna, kna, pna, ps, lane);
-    wide_load<D>(nb, p, m, v, rnb, knb, pnb, ps, lane);
-    wide_replay_pair<D, DW>(xa, ka, pa, xb, kb, pb, T, table, wd, b2, omb2, eps);
-    wide_store<D>(xa, p, m, v, ra, lane);
-    last[(size_t)(ra) * FBN_RS_I] = T;   // every lane, one address
-    if (ps.pend) ps.pend[(size_t)(ra) * FBN_RS_I] = -1;
-    if (j0 + 1 < cnt) {
-      wide_store<D>(xb, p, m, v, rb, lane);
-      last[(size_t)(rb) * FBN_RS_I] = T;
-      if (ps.pend) ps.pend[(size_t)(rb) * FBN_RS_I] = -1;
-    }
-    xa = na; ra = rna; ka = kna; pa = pna;
-    xb = nb; rb = rnb; kb = knb; pb = pnb;
-  }
 }
 
 // The entries of a batch and where their row claims go (adam_claim2, the prefetch kernels): entry
@@ -1062,168 +942,12 @@ struct ClaimSrc {
   int skip0;
 };
 
-// The claimed rows' catch-up (fbn_adam_catchup, parts = 1): entry i of [0, n_ent) with
-// slot_row[i] != -1 brings its row up to the step.
-template <int D, bool DW>
-__global__ void __launch_bounds__(256) adam_catchup_kernel(float* __restrict__ p, float* __restrict__ m,
-                                                           float* __restrict__ v, const int* __restrict__ slot_row,
-                                                           int n_ent, int F, int* __restrict__ last,
-                                                           const AdamConsts* __restrict__ table,
-                                                           const int* __restrict__ step, float wd, float b2,
-                                                           float omb2, float eps, PendSrc ps) {
-  constexpr int G = D / 4, RPW = 64 / G;
-  __shared__ AdamConsts win[FBN_LAZY_MAX_LAG];
-  const int t = *step;
-  // every row is within F steps of t (the rolling window): only steps [t - F, t) are staged
-  const int w0 = t > F ? t - F : 0;
-  if constexpr (D < 128) {   // the wide-row path reads the constants by scalar loads
-    for (int i = threadIdx.x; i < t - w0; i += blockDim.x) {
-      win[i] = table[w0 + i];
-    }
-    __syncthreads();
-  }
-  const long long n = n_ent;
-  // Each wave takes SCAN entries, one per lane, sorts them by replay start (rows that need no replay
-  // last) with a bitonic network over lane shuffles, and its RPW lane groups replay the sorted rows
-  // RPW at a time: the rows of a round have similar replay lengths (their group finishes together)
-  // and duplicate / padding entries and up-to-date rows cost nothing.
-  // SCAN = 16 at D >= 64 gives ~10 waves per SIMD at C3, enough to hide each round's row loads.
-  constexpr int SCAN = D >= 64 ? 16 : 64;
-  const int lane = threadIdx.x & 63, q = lane % G, grp = lane / G;
-  const long long gw = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const long long nw = ((long long)gridDim.x * blockDim.x) >> 6;
-  for (long long i0 = gw * SCAN; i0 < n; i0 += nw * SCAN) {
-    const long long i = i0 + lane;
-    int r = -1, key = 0x7fffffff, pe = -1;
-    if (lane < SCAN && i < n) {
-      const int sr = slot_row[i];
-      if (sr != -1) r = sr & ~FBN_SLOT_FLAG;
-      if (r >= 0) {
-        const int k0 = last[(size_t)(r) * FBN_RS_I];
-        if (k0 < t) {
-          key = k0;
-          if (ps.pend) pe = ps.pend[(size_t)(r) * FBN_RS_I];
-        }
-      }
-    }
-    const int cnt = __popcll(__ballot(key != 0x7fffffff));
-    if (cnt == 0) continue;
-#pragma unroll
-    for (int kk = 2; kk <= SCAN; kk <<= 1)
-#pragma unroll
-      for (int j = kk >> 1; j > 0; j >>= 1) {
-        const int ok = __shfl_xor(key, j, 64), orr = __shfl_xor(r, j, 64), ope = __shfl_xor(pe, j, 64);
-        const bool up = (lane & kk) == 0, lower = (lane & j) == 0;
-        if (lower == up ? ok < key : ok > key) {
-          key = ok;
-          r = orr;
-          pe = ope;
-        }
-      }
-    if constexpr (D >= 128) {
-      wide_rows<D, DW>(r, key, pe, cnt, t, p, m, v, last, table, wd, b2, omb2, eps, ps, lane);
-      continue;
-    }
-    // rounds of RPW rows, software-pipelined: round j+1's loads are issued before round j's
-    // arithmetic (lanes past cnt load row 0 and store nothing)
-    auto fetch = [&](int j0, int& rr, int& k0, int& pp) {
-      const int src = j0 + grp;
-      const int sl = src < 64 ? src : 0;
-      rr = __shfl(r, sl, 64);
-      k0 = __shfl(key, sl, 64);
-      pp = __shfl(pe, sl, 64);
-      if (src >= cnt) { rr = 0; k0 = 0; pp = -1; }
-    };
-    int rc, kc, pc;
-    fetch(0, rc, kc, pc);
-    RowRegs cur;
-    row_load<D>(cur, p, m, v, rc, q, kc, pc, ps, table);
-    for (int j0 = 0; j0 < cnt; j0 += RPW) {
-      int rn, kn, pn;
-      fetch(j0 + RPW, rn, kn, pn);
-      RowRegs nxt;
-      row_load<D>(nxt, p, m, v, rn, q, kn, pn, ps, table);   // past the last round: row 0, discarded
-      if (j0 + grp < cnt) {
-        row_replay_store<D, DW>(cur, p, m, v, rc, q, kc, pc >= 0, t, win, w0, table, wd, b2, omb2, eps);
-        if (q == 0) {
-          last[(size_t)(rc) * FBN_RS_I] = t;
-          if (ps.pend) ps.pend[(size_t)(rc) * FBN_RS_I] = -1;
-        }
-      }
-      cur = nxt;
-      rc = rn;
-      kc = kn;
-      pc = pn;
-    }
-  }
-}
-
-// Ahead-of-time catch-up of the NEXT batch (single GPU, D >= 128), on the side stream during step
-// t, after step t's claims: a row of the next batch that batch t does not touch (map == -1) takes
-// only zero-gradient steps through step t inclusive -- g = 0 * coef + wd * p, whatever step t's
-// clip coefficient -- so it is brought to last = t + 1 now (same operations, same order: still
-// bit-identical to eager Adam) and step t + 1's claimed-row catch-up finds it up to date.  A row
-// is taken by the entry whose CAS moves last[r] from its old value to t + 1 (duplicates skip).
-template <int D, bool DW>
-__global__ void __launch_bounds__(256) adam_prefetch_kernel(float* __restrict__ p, float* __restrict__ m,
-                                                            float* __restrict__ v, ClaimSrc cs, int n,
-                                                            int* __restrict__ last,
-                                                            const AdamConsts* __restrict__ table,
-                                                            const int* __restrict__ step, float wd, float b2,
-                                                            float omb2, float eps, PendSrc ps) {
-  constexpr int SCAN = 16;
-  const int T = *step + 1;
-  const int lane = threadIdx.x & 63;
-  const long long gw = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const long long nw = ((long long)gridDim.x * blockDim.x) >> 6;
-  for (long long i0 = gw * SCAN; i0 < n; i0 += nw * SCAN) {
-    const long long i = i0 + lane;
-    int r = -1, key = 0x7fffffff, pe = -1;
-    if (lane < SCAN && i < n) {
-      long long id;
-      bool ok;
-      if (cs.lids) {   // owner mode: local rows; rank 0's row 0 is the padding id
-        id = cs.lids[i];
-        ok = id >= 0 && id < cs.V && !(cs.skip0 && id == 0);
-      } else {
-        const long long b = i / (cs.L + 1), tt = i - b * (cs.L + 1);
-        id = tt == 0 ? cs.item[b] : cs.seq[b * cs.L + (tt - 1)];
-        ok = id > 0 && id < cs.V;
-      }
-      if (cs.pre && ok)   // next step's claim, decided now (non-returning, tagged)
-        atomicMax(cs.pre + (size_t)id * FBN_RS_Q, ((unsigned long long)T << 32) | (0xFFFFFFFFull - (unsigned long long)i));
-      if (ok && cs.map[id] == -1) {
-        const int k0 = last[(size_t)(id) * FBN_RS_I];
-        if (k0 < T && atomicCAS(last + (size_t)id * FBN_RS_I, k0, T) == k0) {
-          r = (int)id;
-          key = k0;
-          if (ps.pend) pe = ps.pend[(size_t)(id) * FBN_RS_I];
-        }
-      }
-    }
-    const int cnt = __popcll(__ballot(key != 0x7fffffff));
-    if (cnt == 0) continue;
-#pragma unroll
-    for (int kk = 2; kk <= SCAN; kk <<= 1)
-#pragma unroll
-      for (int j = kk >> 1; j > 0; j >>= 1) {
-        const int ok = __shfl_xor(key, j, 64), orr = __shfl_xor(r, j, 64), ope = __shfl_xor(pe, j, 64);
-        const bool up = (lane & kk) == 0, lower = (lane & j) == 0;
-        if (lower == up ? ok < key : ok > key) {
-          key = ok;
-          r = orr;
-          pe = ope;
-        }
-      }
-    wide_rows<D, DW>(r, key, pe, cnt, T, p, m, v, last, table, wd, b2, omb2, eps, ps, lane);
-  }
-}
-
-// ---- The same ahead-of-time catch-up in two passes (single GPU, with pre-claims: the bench and
-// every trainer step given a next batch of its own shape).  The one-pass kernel above is a chain
-// of dependent round trips per 16-entry scan (id -> map -> last -> returning CAS -> pend -> row
-// loads) replayed two rows at a time by ONE wave per SIMD: it measured 20 % VALU issue over
-// 190-257 us.  Here:
+// ---- Ahead-of-time catch-up of the NEXT batch, on the side stream during step t, after step t's
+// claims: a row of the next batch that batch t does not touch (map == -1) takes only zero-gradient
+// steps through step t inclusive -- g = 0 * coef + wd * p, whatever step t's clip coefficient -- so
+// it is brought to last = t + 1 now (same operations, same order: still bit-identical to eager Adam)
+// and step t + 1's claimed-row catch-up finds it up to date.  With pre-claims (the bench and every
+// trainer step given a next batch of its own shape) it runs in two passes:
 //   pass 1 (adam_pretag_kernel): every entry posts its tagged claim with one non-returning
 //     atomic max -- the smallest entry index of an id wins, as the claim at step t + 1 expects;
 //   pass 2 (adam_prefetch2_kernel): one entry per lane and no atomics: the winning entry of a row
@@ -1231,7 +955,8 @@ __global__ void __launch_bounds__(256) adam_prefetch_kernel(float* __restrict__ 
 //     rows by replay start and replays them FOUR at a time (eight independent update chains per
 //     lane at D = 128) while the next four rows' loads are in flight; the schedule constants of
 //     the last FBN_PF_WIN steps sit in LDS and each step's are read one step ahead.
-// Same operations in the same order per row: bit-identical to the one-pass kernel and to eager.
+// Without them (a next batch of another shape, D >= 128) one pass, adam_prefetch_kernel: a row is
+// taken by the entry whose returning CAS moves last[r] to T.
 #define FBN_PF_WIN 256
 
 // entry i's row, or -1: the batch's ids (item, then history slots; 0 = padding), or in owner mode
@@ -1325,9 +1050,6 @@ __device__ __forceinline__ void adam_tabk(typename FVec<N>::T& pp, typename FVec
 }
 __device__ __forceinline__ f32x4 consts4(const AdamConsts& k) { return (f32x4){k.w1, k.nss, k.rbc2s, k.dmul}; }
 
-#ifndef FBN_REPLAY_BLOCK4
-#define FBN_REPLAY_BLOCK4 1   // build-time A/B (build.py VARIANTS "rstep1": 0 = one step per constant load)
-#endif
 // One group of the replay engine: G wave-wide rows (cur, rows cr, replay starts ck, deferred
 // vectors cp; slots past cnt carry row 0 and no steps) brought to T, then stored.
 #define FBN_REPLAY_G 4   // rows per group: eight independent update chains per lane at D = 128
@@ -1354,7 +1076,6 @@ __device__ __forceinline__ void replay_group(WideRow<D> (&cur)[FBN_REPLAY_G], co
   // rows 0..k from ck[k] to ck[k+1] (ck[G] = T): the longest row never replays alone while a later
   // row could join it, and no step waits on its own constants' load.
   int s = ck[0] < T ? ck[0] : T;
-#if FBN_REPLAY_BLOCK4
   // steps in blocks of four: the next block's four constant sets are loaded while this block runs,
   // so a scalar-cache miss (every other step: 32-B records) is hidden behind four steps of the
   // update chains instead of one; the partial last block of a phase uses the block's own sets
@@ -1396,19 +1117,6 @@ __device__ __forceinline__ void replay_group(WideRow<D> (&cur)[FBN_REPLAY_G], co
       ++s;
     }
   }
-#else
-  f32x4 kc = consts4(table[s]);   // table row T exists
-#pragma unroll
-  for (int k = 0; k < G; ++k) {
-    const int send = k + 1 < G ? min(ck[k + 1], T) : T;
-    for (; s < send; ++s) {
-      const f32x4 kn = consts4(table[s + 1]);   // a step ahead
-#pragma unroll
-      for (int x = 0; x <= k; ++x) adam_tabk<DW, N>(cur[x].p, cur[x].m, cur[x].v, zero, wd, b2, omb2, eps, kc);
-      kc = kn;
-    }
-  }
-#endif
 #pragma unroll
   for (int x = 0; x < G; ++x)
     if (j0 + x < cnt) wide_store<D>(cur[x], p, m, v, cr[x], lane);
@@ -1424,19 +1132,7 @@ __device__ __forceinline__ void replay4_sorted(int r, int key, int pe, int cnt, 
                                                const AdamConsts* __restrict__ table, float wd, float b2,
                                                float omb2, float eps, const PendSrc& ps, int lane) {
   constexpr int G = FBN_REPLAY_G;
-  // ascending replay start (descending replay length); rows past cnt last
-#pragma unroll
-  for (int kk = 2; kk <= 64; kk <<= 1)
-#pragma unroll
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      const int ok = __shfl_xor(key, j, 64), orr = __shfl_xor(r, j, 64), ope = __shfl_xor(pe, j, 64);
-      const bool up = (lane & kk) == 0, lower = (lane & j) == 0;
-      if (lower == up ? ok < key : ok > key) {
-        key = ok;
-        r = orr;
-        pe = ope;
-      }
-    }
+  FBN_SORT_ROWS(r, key, pe, lane);   // ascending replay start (descending replay length); rows past cnt last
   // group slot x of the rows at j0: (row, first zero step, deferred vector); past cnt: row 0, no steps
   auto get = [&](int idx, int& rr, int& kk, int& pp) {   // idx wave-uniform
     const int sl = idx < cnt ? idx : 0;
@@ -1476,18 +1172,7 @@ __device__ __forceinline__ void replay_narrow_sorted(int r, int key, int pe, int
                                                      const AdamConsts* __restrict__ table, float wd, float b2,
                                                      float omb2, float eps, const PendSrc& ps, int lane) {
   constexpr int G = D / 4, RPW = 64 / G;
-#pragma unroll
-  for (int kk = 2; kk <= 64; kk <<= 1)
-#pragma unroll
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      const int ok = __shfl_xor(key, j, 64), orr = __shfl_xor(r, j, 64), ope = __shfl_xor(pe, j, 64);
-      const bool up = (lane & kk) == 0, lower = (lane & j) == 0;
-      if (lower == up ? ok < key : ok > key) {
-        key = ok;
-        r = orr;
-        pe = ope;
-      }
-    }
+  FBN_SORT_ROWS(r, key, pe, lane);
   const int q = lane % G, grp = lane / G;
   auto fetch = [&](int j0, int& rr, int& kk, int& pp) {
     const int src = j0 + grp;
@@ -1503,8 +1188,9 @@ __device__ __forceinline__ void replay_narrow_sorted(int r, int key, int pe, int
     x.p = *reinterpret_cast<const f32x4*>(p + off);
     x.m = *reinterpret_cast<const f32x4*>(m + off);
     x.v = *reinterpret_cast<const f32x4*>(v + off);
+    // pend_load, written out (through the helper the narrow engine compiled to other code)
     const int k0 = pp >= 0 ? kk - 1 : kk;   // the deferred gradient's step
-    const float* ring = ps.ring ? ps.ring : p;   // branch-free, as row_load
+    const float* ring = ps.ring ? ps.ring : p;
     const float* coef = ps.coef_hist ? ps.coef_hist : p;
     const size_t go = pp >= 0 ? (size_t)(k0 % ps.ring_n) * ps.ring_stride + (size_t)pp * D : 0;
     x.g = ring_load<f32x4, 4>(ring, ps.bf16, go + 4 * q);
@@ -1583,14 +1269,7 @@ __device__ __forceinline__ void adam_prefetch2_body(float* __restrict__ p, float
       const int4 rs = row_state(last, id);   // tag, last, pend: one 16-B load
       const unsigned long long pv = ((unsigned long long)(unsigned)rs.y << 32) | (unsigned)rs.x;
       if ((int)(pv >> 32) == T && (0xFFFFFFFFu - (unsigned)pv) == (unsigned)i && cs.map[id] == -1) {
-        const int k0 = rs.z;
-        if (k0 < T) {   // this entry owns the row: its replay through step T - 1
-          r = (int)id;
-          if (ps.pend) pe = rs.w;
-          key = k0 + (pe >= 0 ? 1 : 0);   // first zero-gradient step (after the deferred one)
-          last[(size_t)(id) * FBN_RS_I] = T;
-          if (pe >= 0) ps.pend[(size_t)(id) * FBN_RS_I] = -1;
-        }
+        if (rs.z < T) take_row(r, key, pe, id, rs, T, last, ps);   // this entry owns the row: its replay through step T - 1
       }
     }
   }
@@ -1607,6 +1286,36 @@ __global__ void __launch_bounds__(256) adam_prefetch2_kernel(float* __restrict__
                                                              const int* __restrict__ step, float wd, float b2,
                                                              float omb2, float eps, PendSrc ps, int epw) {
   adam_prefetch2_body<D, DW>(p, m, v, cs, n, last, table, step, wd, b2, omb2, eps, ps, epw, blockIdx.x, gridDim.x);
+}
+// The one-pass form (no pre-claims; D >= 128): one entry per lane, 64 entries per wave, walked
+// wave-strided; duplicates of a row lose the CAS and skip.
+template <int D, bool DW>
+__global__ void __launch_bounds__(256) adam_prefetch_kernel(float* __restrict__ p, float* __restrict__ m,
+                                                            float* __restrict__ v, ClaimSrc cs, int n,
+                                                            int* __restrict__ last,
+                                                            const AdamConsts* __restrict__ table,
+                                                            const int* __restrict__ step, float wd, float b2,
+                                                            float omb2, float eps, PendSrc ps) {
+  const int T = *step + 1;
+  const int lane = threadIdx.x & 63;
+  const long long nchunk = ((long long)n + 63) / 64;
+  const long long wstride = ((long long)gridDim.x * blockDim.x) >> 6;
+  for (long long ch = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; ch < nchunk; ch += wstride) {
+    const long long i = ch * 64 + lane;
+    int r = 0, key = 0x7fffffff, pe = -1;
+    if (i < n) {
+      const long long id = entry_row(cs, i);
+      if (id >= 0 && cs.map[id] == -1) {
+        const int4 rs = row_state(last, id);
+        // (pend[r] changes only with last[r]: the pair read above is the winner's; take_row stores
+        // last[r] = T once more, the value the CAS wrote)
+        if (rs.z < T && atomicCAS(last + (size_t)id * FBN_RS_I, rs.z, T) == rs.z) take_row(r, key, pe, id, rs, T, last, ps);
+      }
+    }
+    const int cnt = __popcll(__ballot(key != 0x7fffffff));
+    if (cnt == 0) continue;
+    replay4_sorted<D, DW>(r, key, pe, cnt, T, 0, nullptr, p, m, v, table, wd, b2, omb2, eps, ps, lane);
+  }
 }
 
 // ---- The prefetch with its replay balanced longest-first (fbn_adam_prefetch_binned, D >= 128).
@@ -1642,14 +1351,7 @@ __global__ void __launch_bounds__(256) adam_pfbin_kernel(ClaimSrc cs, int n, int
       const int4 rs = row_state(last, id);
       const unsigned long long pv = ((unsigned long long)(unsigned)rs.y << 32) | (unsigned)rs.x;
       if ((int)(pv >> 32) == T && (0xFFFFFFFFu - (unsigned)pv) == (unsigned)i && cs.map[id] == -1) {
-        const int k0 = rs.z;
-        if (k0 < T) {
-          r = (int)id;
-          if (ps.pend) pe = rs.w;
-          key = k0 + (pe >= 0 ? 1 : 0);
-          last[(size_t)(id) * FBN_RS_I] = T;
-          if (pe >= 0) ps.pend[(size_t)(id) * FBN_RS_I] = -1;
-        }
+        if (rs.z < T) take_row(r, key, pe, id, rs, T, last, ps);
       }
     }
   }
@@ -1760,6 +1462,8 @@ __device__ __forceinline__ void adam_claim2_body(float* __restrict__ p, float* _
   const long long i = (long long)blk * blockDim.x + threadIdx.x;
   int r = 0, key = 0x7fffffff, pe = -1;
   if (i < n) {
+    // (entry_row and take_row written out: through the helpers this kernel, the step's critical path,
+    // compiled to other code)
     long long id;
     bool ok;
     if (cs.lids) {   // owner mode (N > 1): the received local rows (negative: an empty slot)
@@ -1845,6 +1549,47 @@ __global__ void __launch_bounds__(256) adam_claim2_conv_kernel(float* __restrict
     convert_tile(cj, njobs, blockIdx.x - nclaim);
 }
 
+// The claimed rows' catch-up where the claims were made by another launch (fbn_adam_catchup,
+// parts = 1: the owner of the host-split exchange): adam_claim2 without the claim -- entry i of
+// [0, n_ent) with slot_row[i] != -1 brings its row (named once) up to the step.
+#define FBN_CATCHUP_EPW_WIDE 16
+template <int D, bool DW>
+__global__ void __launch_bounds__(256) adam_catchup_kernel(float* __restrict__ p, float* __restrict__ m,
+                                                           float* __restrict__ v, const int* __restrict__ slot_row,
+                                                           int n_ent, int F, int* __restrict__ last,
+                                                           const AdamConsts* __restrict__ table,
+                                                           const int* __restrict__ step, float wd, float b2,
+                                                           float omb2, float eps, PendSrc ps) {
+  __shared__ f32x4 win[FBN_PF_WIN + 1];
+  const int t = *step;
+  // every row is within F steps of t (the rolling window): only that many steps' constants are staged
+  const int W = F < FBN_PF_WIN ? F : FBN_PF_WIN;
+  const int w0 = t > W ? t - W : 0;
+  const int lane = threadIdx.x & 63;
+  // nearly every entry names a row, so wave-wide rows take FBN_CATCHUP_EPW_WIDE entries per wave (four
+  // groups of the engine): four times the waves replaying side by side
+  constexpr int EPW = D >= 128 ? FBN_CATCHUP_EPW_WIDE : 64;
+  const long long wv = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const long long i = lane < EPW ? wv * EPW + lane : n_ent;
+  int r = 0, key = 0x7fffffff, pe = -1;
+  if (i < n_ent) {
+    const int sr = slot_row[i];
+    const int rr = sr == -1 ? -1 : sr & ~FBN_SLOT_FLAG;
+    if (rr >= 0) {
+      const int4 rs = row_state(last, rr);
+      if (rs.z < t) take_row(r, key, pe, rr, rs, t, last, ps);
+    }
+  }
+  if constexpr (D < 128) {   // as adam_claim2_body: staged only where the block has rows (block-uniform)
+    if (!__syncthreads_or(key != 0x7fffffff)) return;
+    for (int s = threadIdx.x; s <= t - w0; s += blockDim.x) win[s] = consts4(table[w0 + s]);
+    __syncthreads();
+  }
+  const int cnt = __popcll(__ballot(key != 0x7fffffff));
+  if (cnt == 0) return;
+  replay_sorted<D, DW>(r, key, pe, cnt, t, w0, win, p, m, v, table, wd, b2, omb2, eps, ps, lane);
+}
+
 __global__ void __launch_bounds__(256) convert_bf16_kernel_o(ConvJobs jobs, int njobs) {
   convert_tile(jobs, njobs, blockIdx.x);
 }
@@ -1852,7 +1597,8 @@ __global__ void __launch_bounds__(256) convert_bf16_kernel_o(ConvJobs jobs, int 
 // The rolling window (step mod F) with the replay engine: rpw rows per wave
 // (one per lane), so a window of ~1e5 rows (C5's 12.5 M-row shard: 97.7 K rows replaying up to F
 // steps each) spreads over thousands of waves instead of one wave per SIMD; claimed rows are left
-// to their claiming entry.
+// to their claiming entry.  With F = 1, chunk = nrows and no map it is the flush: every row up to
+// the step (rows further back than FBN_PF_WIN steps read the schedule table itself).
 #define FBN_WIN_ROWS 16
 template <int D, bool DW>
 __device__ __forceinline__ void adam_window2_body(float* __restrict__ p, float* __restrict__ m,
@@ -1879,16 +1625,7 @@ __device__ __forceinline__ void adam_window2_body(float* __restrict__ p, float* 
   if (lane < rpw && j < nroll) {
     const long long rr = roll0 + j;
     const int4 rs = row_state(last, rr);
-    if (!map || map[rr] == -1) {
-      const int k0 = rs.z;
-      if (k0 < t) {
-        r = (int)rr;
-        if (ps.pend) pe = rs.w;
-        key = k0 + (pe >= 0 ? 1 : 0);
-        last[(size_t)(rr) * FBN_RS_I] = t;
-        if (pe >= 0) ps.pend[(size_t)(rr) * FBN_RS_I] = -1;
-      }
-    }
+    if ((!map || map[rr] == -1) && rs.z < t) take_row(r, key, pe, rr, rs, t, last, ps);
   }
   const int cnt = __popcll(__ballot(key != 0x7fffffff));
   if (cnt == 0) continue;
@@ -1904,37 +1641,6 @@ __global__ void __launch_bounds__(256) adam_window2_kernel(float* __restrict__ p
                                                            float omb2, float eps, PendSrc ps, int rpw) {
   adam_window2_body<D, DW>(p, m, v, map, nrows, F, chunk, last, table, step, wd, b2, omb2, eps, ps, rpw,
                            blockIdx.x, gridDim.x);
-}
-
-// every row up to `step` (checkpoint / evaluation)
-template <int D, bool DW>
-__global__ void __launch_bounds__(256) adam_flush_kernel(float* __restrict__ p, float* __restrict__ m,
-                                                         float* __restrict__ v, long long nrows, int* __restrict__ last,
-                                                         const AdamConsts* __restrict__ table,
-                                                         const int* __restrict__ step, float wd, float b2, float omb2,
-                                                         float eps, PendSrc ps) {
-  constexpr int G = D / 4, RPW = 64 / G;
-  __shared__ AdamConsts win[FBN_LAZY_MAX_LAG];
-  const int t = *step;
-  const int w0 = t > FBN_LAZY_MAX_LAG ? t - FBN_LAZY_MAX_LAG : 0;
-  for (int i = threadIdx.x; i < t - w0; i += blockDim.x) {
-    win[i] = table[w0 + i];
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63, q = lane % G;
-  const long long gw = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const long long nw = ((long long)gridDim.x * blockDim.x) >> 6;
-  for (long long r0 = gw * RPW; r0 < nrows; r0 += nw * RPW) {
-    const long long r = r0 + lane / G;
-    if (r >= nrows) continue;
-    const int k0 = last[(size_t)(r) * FBN_RS_I];
-    if (k0 >= t) continue;
-    replay_rows<D, DW>(p, m, v, r, q, k0, t, win, w0, table, wd, b2, omb2, eps, ps);
-    if (q == 0) {
-      last[(size_t)(r) * FBN_RS_I] = t;
-      if (ps.pend) ps.pend[(size_t)(r) * FBN_RS_I] = -1;
-    }
-  }
 }
 
 // Touched rows: one group per claiming entry e (slot_row[e] = row | FLAG); gradient =
@@ -2690,10 +2396,75 @@ extern "C" int fbn_step_end(int* step, unsigned long long* rng, double* sumsq, l
 }
 
 
+// ---- lazy table Adam, the entry points.  Each ends in the same replay arguments (last,
+// consts_table, step, wd, beta2, eps, pend, ring, coef_hist, ring_stride, ring_n, decoupled): packed
+// once into a ReplayArgs, whose kernel arguments FBN_RA spells in the kernels' order.
+struct ReplayArgs {
+  int* last;
+  const AdamConsts* table;
+  const int* step;
+  float wd, beta2, omb2, eps;
+  PendSrc ps;
+  int decoupled;
+};
+static inline ReplayArgs make_replay(int* last, const void* consts_table, const int* step, float wd, float beta2,
+                                     float eps, int* pend, const float* ring, const float* coef_hist,
+                                     long long ring_stride, int ring_n, int decoupled) {
+  return ReplayArgs{last, (const AdamConsts*)consts_table, step, wd, beta2, (float)(1.0 - (double)beta2), eps,
+                    make_pend(pend, ring, coef_hist, ring_stride, ring_n), decoupled};
+}
+#define FBN_RA(ra) (ra).last, (ra).table, (ra).step, (ra).wd, (ra).beta2, (ra).omb2, (ra).eps, (ra).ps
+
+// The checks every entry point makes on them: deferred gradients (pend) need their ring and
+// coef_hist, and an entry point with a window F (has_F) needs 1 <= F <= FBN_LAZY_MAX_LAG and a ring
+// of more than F steps (ring_n as passed, flag bits included).  false: the error text is set.
+static bool replay_args_ok(const char* who, bool has_F, int F, const int* pend, const float* ring,
+                           const float* coef_hist, int ring_n) {
+  char msg[160];
+  if (has_F && (F < 1 || F > FBN_LAZY_MAX_LAG)) {
+    snprintf(msg, sizeof(msg), "%s: 1 <= F <= %d", who, FBN_LAZY_MAX_LAG);
+  } else if (pend && (!ring || !coef_hist || (has_F && ring_n <= F))) {
+    snprintf(msg, sizeof(msg), "%s: deferred gradients (pend) need ring and coef_hist%s", who,
+             has_F ? ", and ring_n > F" : "");
+  } else {
+    return true;
+  }
+  fbn_set_error(msg);
+  return false;
+}
+
+// a kernel templated on <D, decoupled>: every D, or the wave-wide rows only (D checked by the caller)
+#define FBN_DISPATCH_D_DW(KERNEL, DW, D, GRID, ...)                                                  \
+  if (DW) { FBN_DISPATCH_D_B(KERNEL, true, D, GRID, __VA_ARGS__) }                                   \
+  else { FBN_DISPATCH_D_B(KERNEL, false, D, GRID, __VA_ARGS__) }
+#define FBN_DISPATCH_WIDE_DW(KERNEL, DW, D, GRID, ...)                                               \
+  if (D == 128) {                                                                                   \
+    if (DW) fbn_launch((KERNEL<128, true>), GRID, dim3(256), 0, st, __VA_ARGS__);                   \
+    else fbn_launch((KERNEL<128, false>), GRID, dim3(256), 0, st, __VA_ARGS__);                     \
+  } else {                                                                                          \
+    if (DW) fbn_launch((KERNEL<256, true>), GRID, dim3(256), 0, st, __VA_ARGS__);                   \
+    else fbn_launch((KERNEL<256, false>), GRID, dim3(256), 0, st, __VA_ARGS__);                     \
+  }
+
+// The rolling window's launch over rows [roll0, roll0 + chunk) of window (step mod F) -- and, with
+// F = 1 and no map, the flush of the whole table.  Rows per wave: wave-wide rows take 8, so more
+// waves replay side by side; below d = 128 a window takes 16 (one round of the narrow engine: a
+// window is small) and the flush a row per lane, on a capped grid that walks the table wave-strided.
+static int launch_window(float* p, float* m, float* v, const int* map, long long nrows, int D, int F, long long chunk,
+                         bool flush, const ReplayArgs& ra, hipStream_t st) {
+  const int rpw = D >= 128 ? 8 : flush ? 64 : FBN_WIN_ROWS;
+  const long long waves = (chunk + rpw - 1) / rpw;
+  const dim3 g2((unsigned)std::min<long long>((waves + 3) / 4, flush ? 16384 : 1ll << 31));
+  FBN_DISPATCH_D_DW(adam_window2_kernel, ra.decoupled, D, g2, p, m, v, map, nrows, F, chunk, FBN_RA(ra), rpw);
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}
+
 // lazy table Adam: replay the zero-loss-gradient steps of the claimed rows and of rolling window
 // (step mod F) (chunk = ceil(nrows / F) rows) up to `step`; last: [nrows] steps applied per row
-// parts: 1 = the claimed rows (must precede the gather), 2 = the rolling window (unclaimed rows:
-// nothing else reads them this step -> may run on a side stream); any other value is FBN_ERR_ARG
+// parts: 1 = the claimed rows (must precede the gather): entry i of slot_row [n_ent] names a row
+// (each at most once) or is -1; 2 = the rolling window (unclaimed rows: nothing else reads them this
+// step -> may run on a side stream); any other value is FBN_ERR_ARG
 extern "C" int fbn_adam_catchup(float* p, float* m, float* v, long long nrows, int D, const int* slot_row, int n_ent,
                                 const int* map, int F, int parts, int* last, const void* consts_table, const int* step,
                                 float wd, float beta2, float eps, int* pend, const float* ring,
@@ -2706,49 +2477,58 @@ extern "C" int fbn_adam_catchup(float* p, float* m, float* v, long long nrows, i
     return FBN_ERR_ARG;
   }
   hipStream_t st = (hipStream_t)stream;
-  const float omb2 = (float)(1.0 - (double)beta2);
   const long long chunk = (nrows + F - 1) / F;
-  const long long items = parts == 1 ? n_ent : chunk;
-  if (items <= 0) return FBN_OK;
-  if (pend && (!ring || !coef_hist || ring_n <= F)) {
-    fbn_set_error("fbn_adam_catchup: deferred gradients need ring, coef_hist and ring_n > F");
-    return FBN_ERR_ARG;
-  }
-  const PendSrc ps = make_pend(pend, ring, coef_hist, ring_stride, ring_n);
-  if (parts == 2) {
-    // the window runs beside the step, on the replay engine.  Rows per wave: 16 below d = 128 (one
-    // round of the narrow engine); wave-wide rows take 8, so more waves replay side by side
-    const int rpw = D >= 128 ? 8 : FBN_WIN_ROWS;
-    const long long waves = (chunk + rpw - 1) / rpw;
-    const dim3 g2((unsigned)((waves + 3) / 4));
-    if (decoupled) {
-      FBN_DISPATCH_D_B(adam_window2_kernel, true, D, g2, p, m, v, map, nrows, F, chunk, last,
-                       (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps, rpw);
-    } else {
-      FBN_DISPATCH_D_B(adam_window2_kernel, false, D, g2, p, m, v, map, nrows, F, chunk, last,
-                       (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps, rpw);
-    }
-    FBN_CHECK_LAUNCH();
-    return FBN_OK;
-  }
-  // one wave per SCAN entries (16 at D >= 64, else 64; sorted and compacted inside the kernel)
-  const long long scan = D >= 64 ? 16 : 64;
-  const dim3 grid((unsigned)std::min<long long>(8192, (items + 4 * scan - 1) / (4 * scan)));
-  if (decoupled) {
-    FBN_DISPATCH_D_B(adam_catchup_kernel, true, D, grid, p, m, v, slot_row, n_ent, F, last,
-                     (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps);
-  } else {
-    FBN_DISPATCH_D_B(adam_catchup_kernel, false, D, grid, p, m, v, slot_row, n_ent, F, last,
-                     (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps);
-  }
+  if ((parts == 1 ? (long long)n_ent : chunk) <= 0) return FBN_OK;
+  if (!replay_args_ok("fbn_adam_catchup", true, F, pend, ring, coef_hist, ring_n)) return FBN_ERR_ARG;
+  const ReplayArgs ra = make_replay(last, consts_table, step, wd, beta2, eps, pend, ring, coef_hist, ring_stride,
+                                    ring_n, decoupled);
+  if (parts == 2) return launch_window(p, m, v, map, nrows, D, F, chunk, false, ra, st);
+  const int epw = D >= 128 ? FBN_CATCHUP_EPW_WIDE : 64;   // entries per wave, four waves per block
+  const dim3 grid((unsigned)((((long long)n_ent + epw - 1) / epw + 3) / 4));
+  FBN_DISPATCH_D_DW(adam_catchup_kernel, decoupled, D, grid, p, m, v, slot_row, n_ent, F, FBN_RA(ra));
   FBN_CHECK_LAUNCH();
   return FBN_OK;
 }
 
-// single GPU, D >= 128: ahead-of-time catch-up of the next batch's rows (adam_prefetch_kernel);
-// call on the stream of the rolling window, after this step's claims and before its step tail
-// ---- fbn_adam_prefetch_binned: the two-pass prefetch with the longest-first replay (adam_pfbin +
-// adam_pfreplay).  Workspace: the (bin, copy) counters, one 128-B line each, then the record lists.
+// every row up to `step` (checkpoint / evaluation): the window pass over the whole table
+extern "C" int fbn_adam_flush(float* p, float* m, float* v, long long nrows, int D, int* last, const void* consts_table,
+                              const int* step, float wd, float beta2, float eps, int* pend, const float* ring,
+                              const float* coef_hist, long long ring_stride, int ring_n, int decoupled,
+                              void* stream) {
+  if (nrows <= 0) return FBN_OK;
+  const ReplayArgs ra = make_replay(last, consts_table, step, wd, beta2, eps, pend, ring, coef_hist, ring_stride,
+                                    ring_n, decoupled);
+  return launch_window(p, m, v, nullptr, nrows, D, 1, nrows, true, ra, (hipStream_t)stream);
+}
+
+// ---- the prefetches' launches (fbn_adam_prefetch, fbn_adam_prefetch_rows, fbn_adam_prefetch_binned)
+static void launch_pretag(const ClaimSrc& cs, long long n, const int* step, hipStream_t st) {
+  fbn_launch(adam_pretag_kernel, dim3((unsigned)((n + FBN_PRETAG_BLOCK - 1) / FBN_PRETAG_BLOCK)),
+             dim3(FBN_PRETAG_BLOCK), 0, st, cs, (int)n, step);
+}
+// with pre-claims, the two passes (adam_pretag + adam_prefetch2): tagged pre-claims decide each row's
+// owning entry with one non-returning atomic, the replay engine takes 64 entries per wave
+static int launch_prefetch2(const ClaimSrc& cs, long long n, float* p, float* m, float* v, int D, const ReplayArgs& ra,
+                            hipStream_t st) {
+  launch_pretag(cs, n, ra.step, st);
+  FBN_CHECK_LAUNCH();
+  const int epw = 64;   // entries per wave
+  const dim3 g3((unsigned)(((n + epw - 1) / epw + 3) / 4));   // 4 waves per block
+  FBN_DISPATCH_D_DW(adam_prefetch2_kernel, ra.decoupled, D, g3, p, m, v, cs, (int)n, FBN_RA(ra), epw);
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}
+// without them, D = 128 / 256: one pass (adam_prefetch_kernel), 64 entries per wave as well
+static int launch_prefetch1(const ClaimSrc& cs, long long n, float* p, float* m, float* v, int D, const ReplayArgs& ra,
+                            hipStream_t st) {
+  const dim3 grid((unsigned)(((n + 63) / 64 + 3) / 4));
+  FBN_DISPATCH_WIDE_DW(adam_prefetch_kernel, ra.decoupled, D, grid, p, m, v, cs, (int)n, FBN_RA(ra));
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}
+
+// the two-pass prefetch with the longest-first replay (adam_pfbin + adam_pfreplay).  Workspace: the
+// (bin, copy) counters, one 128-B line each, then the record lists.
 static long long pfb_records_per_list(long long n) {
   const long long nblk = (n + 255) / 256;
   return (nblk + FBN_PFB_NC - 1) / FBN_PFB_NC * 256;
@@ -2756,39 +2536,6 @@ static long long pfb_records_per_list(long long n) {
 extern "C" size_t fbn_adam_prefetch_binned_ws_size(long long n) {
   const size_t cnt = (size_t)FBN_PFB_NB * FBN_PFB_NC * FBN_PFB_LINE * sizeof(unsigned);
   return cnt + (size_t)FBN_PFB_NB * FBN_PFB_NC * pfb_records_per_list(n) * sizeof(int4);
-}
-
-static int launch_prefetch_binned(const ClaimSrc& cs, long long n, float* p, float* m, float* v, int D, int* last,
-                                  const void* consts_table, const int* step, float wd, float beta2, float eps,
-                                  const PendSrc& ps, int decoupled, void* ws, size_t ws_bytes, hipStream_t st) {
-  if (ws_bytes < fbn_adam_prefetch_binned_ws_size(n) || !ws) {
-    fbn_set_error("fbn_adam_prefetch_binned: workspace smaller than fbn_adam_prefetch_binned_ws_size(n)");
-    return FBN_ERR_ARG;
-  }
-  const float omb2 = (float)(1.0 - (double)beta2);
-  unsigned* counts = (unsigned*)ws;
-  int4* recs = (int4*)((char*)ws + (size_t)FBN_PFB_NB * FBN_PFB_NC * FBN_PFB_LINE * sizeof(unsigned));
-  const int nblk = (int)((n + 255) / 256);
-  fbn_launch(pfb_zero_kernel, dim3(1), dim3(256), 0, st, counts);
-  fbn_launch(adam_pretag_kernel, dim3((unsigned)((n + FBN_PRETAG_BLOCK - 1) / FBN_PRETAG_BLOCK)),
-             dim3(FBN_PRETAG_BLOCK), 0, st, cs, (int)n, step);
-  fbn_launch(adam_pfbin_kernel, dim3(nblk), dim3(256), 0, st, cs, (int)n, last, step, ps, counts, recs);
-  const int ch = 32;   // records per replay wave (see adam_pfreplay_kernel)
-  // at most one chunk per ch records plus one partial chunk per list
-  const long long waves = (n + ch - 1) / ch + FBN_PFB_NB * FBN_PFB_NC;
-  const dim3 g((unsigned)((waves + 3) / 4));
-  const AdamConsts* tab = (const AdamConsts*)consts_table;
-#define FBN_PFB_LAUNCH(D_, DW_)                                                                              \
-  fbn_launch((adam_pfreplay_kernel<D_, DW_>), g, dim3(256), 0, st, p, m, v, step, wd, beta2, omb2, eps, tab, ps, \
-             (const unsigned*)counts, (const int4*)recs, nblk, ch)
-  if (D == 128) {
-    if (decoupled) FBN_PFB_LAUNCH(128, true); else FBN_PFB_LAUNCH(128, false);
-  } else {
-    if (decoupled) FBN_PFB_LAUNCH(256, true); else FBN_PFB_LAUNCH(256, false);
-  }
-#undef FBN_PFB_LAUNCH
-  FBN_CHECK_LAUNCH();
-  return FBN_OK;
 }
 
 extern "C" int fbn_adam_prefetch_binned(const int64_t* item, const int64_t* seq, int B, int L, long long V,
@@ -2807,13 +2554,33 @@ extern "C" int fbn_adam_prefetch_binned(const int64_t* item, const int64_t* seq,
     fbn_set_error("fbn_adam_prefetch_binned: item, seq (L > 0), map, last and preclaim are required");
     return FBN_ERR_ARG;
   }
-  if (pend && (!ring || !coef_hist)) { fbn_set_error("fbn_adam_prefetch_binned: pend needs ring and coef_hist"); return FBN_ERR_ARG; }
-  const PendSrc ps = make_pend(pend, ring, coef_hist, ring_stride, ring_n);
+  if (!replay_args_ok("fbn_adam_prefetch_binned", false, 0, pend, ring, coef_hist, ring_n)) return FBN_ERR_ARG;
+  if (ws_bytes < fbn_adam_prefetch_binned_ws_size(n) || !ws) {
+    fbn_set_error("fbn_adam_prefetch_binned: workspace smaller than fbn_adam_prefetch_binned_ws_size(n)");
+    return FBN_ERR_ARG;
+  }
+  const ReplayArgs ra = make_replay(last, consts_table, step, wd, beta2, eps, pend, ring, coef_hist, ring_stride,
+                                    ring_n, decoupled);
   const ClaimSrc cs{item, L > 0 ? seq : nullptr, L, V, const_cast<int*>(map), nullptr, nullptr, nullptr, preclaim};
-  return launch_prefetch_binned(cs, n, p, m, v, D, last, consts_table, step, wd, beta2, eps, ps, decoupled, ws,
-                                ws_bytes, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  unsigned* counts = (unsigned*)ws;
+  int4* recs = (int4*)((char*)ws + (size_t)FBN_PFB_NB * FBN_PFB_NC * FBN_PFB_LINE * sizeof(unsigned));
+  const int nblk = (int)((n + 255) / 256);
+  fbn_launch(pfb_zero_kernel, dim3(1), dim3(256), 0, st, counts);
+  launch_pretag(cs, n, step, st);
+  fbn_launch(adam_pfbin_kernel, dim3(nblk), dim3(256), 0, st, cs, (int)n, last, step, ra.ps, counts, recs);
+  const int ch = 32;   // records per replay wave (see adam_pfreplay_kernel)
+  // at most one chunk per ch records plus one partial chunk per list
+  const long long waves = (n + ch - 1) / ch + FBN_PFB_NB * FBN_PFB_NC;
+  const dim3 g((unsigned)((waves + 3) / 4));
+  FBN_DISPATCH_WIDE_DW(adam_pfreplay_kernel, decoupled, D, g, p, m, v, step, wd, beta2, ra.omb2, eps, ra.table,
+                       ra.ps, (const unsigned*)counts, (const int4*)recs, nblk, ch);
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
 }
 
+// single GPU: ahead-of-time catch-up of the next batch's rows; call on the stream of the rolling
+// window, after this step's claims and before its step tail
 extern "C" int fbn_adam_prefetch(const int64_t* item, const int64_t* seq, int B, int L, long long V, const int* map,
                                  unsigned long long* preclaim, float* p, float* m, float* v, int D, int* last,
                                  const void* consts_table, const int* step, float wd, float beta2, float eps, int* pend,
@@ -2833,51 +2600,17 @@ extern "C" int fbn_adam_prefetch(const int64_t* item, const int64_t* seq, int B,
     fbn_set_error("fbn_adam_prefetch: item, seq (L > 0), map and last are required");
     return FBN_ERR_ARG;
   }
-  if (pend && (!ring || !coef_hist)) { fbn_set_error("fbn_adam_prefetch: pend needs ring and coef_hist"); return FBN_ERR_ARG; }
-  const float omb2 = (float)(1.0 - (double)beta2);
-  const PendSrc ps = make_pend(pend, ring, coef_hist, ring_stride, ring_n);
+  if (!replay_args_ok("fbn_adam_prefetch", false, 0, pend, ring, coef_hist, ring_n)) return FBN_ERR_ARG;
+  const ReplayArgs ra = make_replay(last, consts_table, step, wd, beta2, eps, pend, ring, coef_hist, ring_stride,
+                                    ring_n, decoupled);
   const ClaimSrc cs{item, L > 0 ? seq : nullptr, L, V, const_cast<int*>(map), nullptr, nullptr, nullptr, preclaim};
-  hipStream_t st = (hipStream_t)stream;
-  if (preclaim) {   // with pre-claims: the two-pass form
-    fbn_launch(adam_pretag_kernel, dim3((unsigned)((n + FBN_PRETAG_BLOCK - 1) / FBN_PRETAG_BLOCK)),
-               dim3(FBN_PRETAG_BLOCK), 0, st, cs, (int)n, step);
-    FBN_CHECK_LAUNCH();
-    const int epw = 64;   // entries per wave
-    const long long waves = (n + epw - 1) / epw;
-    const dim3 g3((unsigned)((waves + 3) / 4));   // 4 waves per block
-    if (decoupled) {
-      FBN_DISPATCH_D_B(adam_prefetch2_kernel, true, D, g3, p, m, v, cs, (int)n, last, (const AdamConsts*)consts_table,
-                       step, wd, beta2, omb2, eps, ps, epw);
-    } else {
-      FBN_DISPATCH_D_B(adam_prefetch2_kernel, false, D, g3, p, m, v, cs, (int)n, last, (const AdamConsts*)consts_table,
-                       step, wd, beta2, omb2, eps, ps, epw);
-    }
-    FBN_CHECK_LAUNCH();
-    return FBN_OK;
-  }
-  const dim3 grid((unsigned)std::min<long long>(256, (n + 63) / 64));   // D >= 128 without pre-claims: one pass
-  if (D == 128) {
-    if (decoupled)
-      fbn_launch((adam_prefetch_kernel<128, true>), grid, dim3(256), 0, st, p, m, v, cs, (int)n, last,
-                         (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps);
-    else
-      fbn_launch((adam_prefetch_kernel<128, false>), grid, dim3(256), 0, st, p, m, v, cs, (int)n, last,
-                         (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps);
-  } else {
-    if (decoupled)
-      fbn_launch((adam_prefetch_kernel<256, true>), grid, dim3(256), 0, st, p, m, v, cs, (int)n, last,
-                         (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps);
-    else
-      fbn_launch((adam_prefetch_kernel<256, false>), grid, dim3(256), 0, st, p, m, v, cs, (int)n, last,
-                         (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps);
-  }
-  FBN_CHECK_LAUNCH();
-  return FBN_OK;
+  return (preclaim ? launch_prefetch2 : launch_prefetch1)(cs, n, p, m, v, D, ra, (hipStream_t)stream);
 }
 
 // N > 1 (the owner's side): the same ahead-of-time catch-up over the local rows the NEXT step's
 // requests name (lids [n], -1 = none: the padded id exchange of RowExchange.prepare); rows this
-// step's requests claimed (map != -1) are left to the next step's claimed-row catch-up
+// step's requests claimed (map != -1) are left to the next step's claimed-row catch-up.  The tags
+// of the two-pass form only decide this pass: the next step's owner claims do not read them.
 extern "C" int fbn_adam_prefetch_rows(const int* lids, int n, int skip0, long long nrows, const int* map,
                                       unsigned long long* preclaim, float* p, float* m, float* v, int D, int* last,
                                       const void* consts_table, const int* step, float wd, float beta2, float eps,
@@ -2886,64 +2619,51 @@ extern "C" int fbn_adam_prefetch_rows(const int* lids, int n, int skip0, long lo
   if (n <= 0 || nrows <= 0) return FBN_OK;
   if (D != 128 && D != 256) { fbn_set_error("fbn_adam_prefetch_rows: D = 128 or 256"); return FBN_ERR_ARG; }
   if (!lids || !map || !last) { fbn_set_error("fbn_adam_prefetch_rows: lids, map and last are required"); return FBN_ERR_ARG; }
-  if (pend && (!ring || !coef_hist)) {
-    fbn_set_error("fbn_adam_prefetch_rows: pend needs ring and coef_hist");
-    return FBN_ERR_ARG;
-  }
-  const float omb2 = (float)(1.0 - (double)beta2);
-  const PendSrc ps = make_pend(pend, ring, coef_hist, ring_stride, ring_n);
-  ClaimSrc cs{nullptr, nullptr, 0, nrows, const_cast<int*>(map), nullptr, nullptr, nullptr, nullptr};
+  if (!replay_args_ok("fbn_adam_prefetch_rows", false, 0, pend, ring, coef_hist, ring_n)) return FBN_ERR_ARG;
+  const ReplayArgs ra = make_replay(last, consts_table, step, wd, beta2, eps, pend, ring, coef_hist, ring_stride,
+                                    ring_n, decoupled);
+  ClaimSrc cs{nullptr, nullptr, 0, nrows, const_cast<int*>(map), nullptr, nullptr, nullptr, preclaim};
   cs.lids = lids;
   cs.skip0 = skip0;
-  hipStream_t st = (hipStream_t)stream;
-  if (preclaim) {
-    // the two passes of the single-GPU prefetch (adam_pretag + adam_prefetch2): tagged pre-claims
-    // decide each row's owning entry with one non-returning atomic, the four-row engine replays
-    // (round 3's one-pass kernel: a returning CAS per entry and 16-entry scans, ~174 us per step at
-    // one rank).  The tags only decide this pass: the next step's owner claims do not read them.
-    cs.pre = preclaim;
-    const dim3 g2((unsigned)((n + 255) / 256));
-    fbn_launch(adam_pretag_kernel, dim3((unsigned)((n + FBN_PRETAG_BLOCK - 1) / FBN_PRETAG_BLOCK)),
-               dim3(FBN_PRETAG_BLOCK), 0, st, cs, n, step);
-    const int epw = 64;
-    const dim3 g3((unsigned)(((n + epw - 1) / epw + 3) / 4));
-    if (decoupled) {
-      FBN_DISPATCH_D_B(adam_prefetch2_kernel, true, D, g3, p, m, v, cs, n, last, (const AdamConsts*)consts_table,
-                       step, wd, beta2, omb2, eps, ps, epw);
-    } else {
-      FBN_DISPATCH_D_B(adam_prefetch2_kernel, false, D, g3, p, m, v, cs, n, last, (const AdamConsts*)consts_table,
-                       step, wd, beta2, omb2, eps, ps, epw);
-    }
-    FBN_CHECK_LAUNCH();
-    return FBN_OK;
-  }
-  const dim3 grid((unsigned)std::min<long long>(256, ((long long)n + 63) / 64));
-  if (D == 128) {
-    if (decoupled)
-      fbn_launch((adam_prefetch_kernel<128, true>), grid, dim3(256), 0, st, p, m, v, cs, n, last,
-                         (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps);
-    else
-      fbn_launch((adam_prefetch_kernel<128, false>), grid, dim3(256), 0, st, p, m, v, cs, n, last,
-                         (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps);
-  } else {
-    if (decoupled)
-      fbn_launch((adam_prefetch_kernel<256, true>), grid, dim3(256), 0, st, p, m, v, cs, n, last,
-                         (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps);
-    else
-      fbn_launch((adam_prefetch_kernel<256, false>), grid, dim3(256), 0, st, p, m, v, cs, n, last,
-                         (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps);
-  }
-  FBN_CHECK_LAUNCH();
-  return FBN_OK;
+  return (preclaim ? launch_prefetch2 : launch_prefetch1)(cs, n, p, m, v, D, ra, (hipStream_t)stream);
 }
 
-// single GPU: fbn_claim_rows + fbn_adam_catchup(parts = 1) in one launch (see ClaimSrc)
+// single GPU: fbn_claim_rows + fbn_adam_catchup(parts = 1) in one launch (see ClaimSrc), one entry
+// per lane (adam_claim2_kernel); with conversion jobs, those ride in the same launch
 static int claim_catchup_impl(const int64_t* item, const int64_t* seq, int B, int L, long long V, int* map,
                               int* slot_row, int* dup, int* hasdup, unsigned long long* preclaim, float* p, float* m,
                               float* v, long long nrows, int D, int F, int* last, const void* consts_table,
                               const int* step, float wd, float beta2, float eps, int* pend, const float* ring,
                               const float* coef_hist, long long ring_stride, int ring_n, int decoupled,
-                              const void* conv_jobs, int n_conv, void* stream);
+                              const void* conv_jobs, int n_conv, void* stream) {
+  const long long n = (long long)B * (L + 1);
+  ConvJobs cj;
+  const int conv_tiles = n_conv > 0 ? conv_jobs_pack(conv_jobs, n_conv, cj) : 0;
+  if (conv_tiles > 0 && (n <= 0 || nrows <= 0)) {   // no claim launch to ride on: convert alone
+    fbn_launch(convert_bf16_kernel_o, dim3(conv_tiles), dim3(256), 0, (hipStream_t)stream, cj, n_conv);
+    FBN_CHECK_LAUNCH();
+  }
+  if (n <= 0 || nrows <= 0) return FBN_OK;
+  if (!item || (L > 0 && !seq) || !map || !slot_row) {
+    fbn_set_error("fbn_adam_claim_catchup: item, seq (L > 0), map and slot_row are required");
+    return FBN_ERR_ARG;
+  }
+  if (!replay_args_ok("fbn_adam_claim_catchup", true, F, pend, ring, coef_hist, ring_n)) return FBN_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const ReplayArgs ra = make_replay(last, consts_table, step, wd, beta2, eps, pend, ring, coef_hist, ring_stride,
+                                    ring_n, decoupled);
+  const ClaimSrc cs{item, L > 0 ? seq : nullptr, L, V, map, slot_row, dup, hasdup, preclaim};
+  const int nclaim = (int)((n + 255) / 256);
+  if (conv_tiles > 0) {
+    const dim3 g2((unsigned)(nclaim + conv_tiles));
+    FBN_DISPATCH_D_DW(adam_claim2_conv_kernel, decoupled, D, g2, p, m, v, cs, (int)n, FBN_RA(ra), cj, n_conv, nclaim);
+  } else {
+    const dim3 g2((unsigned)nclaim);
+    FBN_DISPATCH_D_DW(adam_claim2_kernel, decoupled, D, g2, p, m, v, cs, (int)n, FBN_RA(ra));
+  }
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}
 
 extern "C" int fbn_adam_claim_catchup(const int64_t* item, const int64_t* seq, int B, int L, long long V, int* map,
                                       int* slot_row, int* dup, int* hasdup, unsigned long long* preclaim, float* p,
@@ -2954,45 +2674,6 @@ extern "C" int fbn_adam_claim_catchup(const int64_t* item, const int64_t* seq, i
   return claim_catchup_impl(item, seq, B, L, V, map, slot_row, dup, hasdup, preclaim, p, m, v, nrows, D, F, last,
                             consts_table, step, wd, beta2, eps, pend, ring, coef_hist, ring_stride, ring_n, decoupled,
                             nullptr, 0, stream);
-}
-
-// N > 1 owner, the fixed-capacity exchange: the claims of the received local rows (lids [n], negative =
-// empty slot; rank 0's row 0 is padding when skip0) and the claimed-row catch-up in ONE launch, as
-// fbn_adam_claim_catchup does for the single GPU.  preclaim (optional): the tags
-// fbn_adam_prefetch_rows posted during the previous step for this very routing (its entry indices
-// are these slots): a row tagged for this step is claimed by its smallest slot without a CAS.
-extern "C" int fbn_adam_owner_claim_catchup(const int* lids, int n, int skip0, int* map, int* slot_row,
-                                            unsigned long long* preclaim, float* p, float* m, float* v,
-                                            long long nrows, int D, int F, int* last, const void* consts_table,
-                                            const int* step, float wd, float beta2, float eps, int* pend,
-                                            const float* ring, const float* coef_hist, long long ring_stride,
-                                            int ring_n, int decoupled, void* stream) {
-  if (n <= 0 || nrows <= 0) return FBN_OK;
-  if (!lids || !map || !slot_row || !last) {
-    fbn_set_error("fbn_adam_owner_claim_catchup: lids, map, slot_row and last are required");
-    return FBN_ERR_ARG;
-  }
-  if (F < 1 || F > FBN_LAZY_MAX_LAG) { fbn_set_error("fbn_adam_owner_claim_catchup: 1 <= F <= 512"); return FBN_ERR_ARG; }
-  if (pend && (!ring || !coef_hist || ring_n <= F)) {
-    fbn_set_error("fbn_adam_owner_claim_catchup: deferred gradients need ring, coef_hist and ring_n > F");
-    return FBN_ERR_ARG;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const float omb2 = (float)(1.0 - (double)beta2);
-  const PendSrc ps = make_pend(pend, ring, coef_hist, ring_stride, ring_n);
-  ClaimSrc cs{nullptr, nullptr, 0, nrows, map, slot_row, nullptr, nullptr, preclaim};
-  cs.lids = lids;
-  cs.skip0 = skip0;
-  const dim3 g2((unsigned)((n + 255) / 256));
-  if (decoupled) {
-    FBN_DISPATCH_D_B(adam_claim2_kernel, true, D, g2, p, m, v, cs, n, last, (const AdamConsts*)consts_table, step, wd,
-                     beta2, omb2, eps, ps);
-  } else {
-    FBN_DISPATCH_D_B(adam_claim2_kernel, false, D, g2, p, m, v, cs, n, last, (const AdamConsts*)consts_table, step,
-                     wd, beta2, omb2, eps, ps);
-  }
-  FBN_CHECK_LAUNCH();
-  return FBN_OK;
 }
 
 extern "C" int fbn_adam_claim_catchup_conv(const int64_t* item, const int64_t* seq, int B, int L, long long V,
@@ -3012,74 +2693,31 @@ extern "C" int fbn_adam_claim_catchup_conv(const int64_t* item, const int64_t* s
                             conv_jobs, n_conv, stream);
 }
 
-static int claim_catchup_impl(const int64_t* item, const int64_t* seq, int B, int L, long long V, int* map,
-                              int* slot_row, int* dup, int* hasdup, unsigned long long* preclaim, float* p, float* m,
-                              float* v, long long nrows, int D, int F, int* last, const void* consts_table,
-                              const int* step, float wd, float beta2, float eps, int* pend, const float* ring,
-                              const float* coef_hist, long long ring_stride, int ring_n, int decoupled,
-                              const void* conv_jobs, int n_conv, void* stream) {
-  const long long n = (long long)B * (L + 1);
-  ConvJobs cj;
-  const int conv_tiles = n_conv > 0 ? conv_jobs_pack(conv_jobs, n_conv, cj) : 0;
-  if (conv_tiles > 0 && (n <= 0 || nrows <= 0)) {   // no claim launch to ride on: convert alone
-    fbn_launch(convert_bf16_kernel_o, dim3(conv_tiles), dim3(256), 0, (hipStream_t)stream, cj, n_conv);
-    FBN_CHECK_LAUNCH();
-  }
+// N > 1 owner, the fixed-capacity exchange: the claims of the received local rows (lids [n], negative =
+// empty slot; rank 0's row 0 is padding when skip0) and the claimed-row catch-up in ONE launch, as
+// fbn_adam_claim_catchup does for the single GPU.  preclaim (optional): the tags
+// fbn_adam_prefetch_rows posted during the previous step for this very routing (its entry indices
+// are these slots): a row tagged for this step is claimed by its smallest slot without a CAS.
+extern "C" int fbn_adam_owner_claim_catchup(const int* lids, int n, int skip0, int* map, int* slot_row,
+                                            unsigned long long* preclaim, float* p, float* m, float* v,
+                                            long long nrows, int D, int F, int* last, const void* consts_table,
+                                            const int* step, float wd, float beta2, float eps, int* pend,
+                                            const float* ring, const float* coef_hist, long long ring_stride,
+                                            int ring_n, int decoupled, void* stream) {
   if (n <= 0 || nrows <= 0) return FBN_OK;
-  if (!item || (L > 0 && !seq) || !map || !slot_row) {
-    fbn_set_error("fbn_adam_claim_catchup: item, seq (L > 0), map and slot_row are required");
+  if (!lids || !map || !slot_row || !last) {
+    fbn_set_error("fbn_adam_owner_claim_catchup: lids, map, slot_row and last are required");
     return FBN_ERR_ARG;
   }
-  if (F < 1 || F > FBN_LAZY_MAX_LAG) { fbn_set_error("fbn_adam_claim_catchup: 1 <= F <= 512"); return FBN_ERR_ARG; }
-  if (pend && (!ring || !coef_hist || ring_n <= F)) {
-    fbn_set_error("fbn_adam_claim_catchup: deferred gradients need ring, coef_hist and ring_n > F");
-    return FBN_ERR_ARG;
-  }
+  if (!replay_args_ok("fbn_adam_owner_claim_catchup", true, F, pend, ring, coef_hist, ring_n)) return FBN_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  const float omb2 = (float)(1.0 - (double)beta2);
-  const PendSrc ps = make_pend(pend, ring, coef_hist, ring_stride, ring_n);
-  const ClaimSrc cs{item, L > 0 ? seq : nullptr, L, V, map, slot_row, dup, hasdup, preclaim};
-  // one entry per lane, row state in one round trip, the replay engine (adam_claim2_kernel)
-  if (conv_tiles > 0) {
-    const int nclaim = (int)((n + 255) / 256);
-    const dim3 g2((unsigned)(nclaim + conv_tiles));
-    if (decoupled) {
-      FBN_DISPATCH_D_B(adam_claim2_conv_kernel, true, D, g2, p, m, v, cs, (int)n, last,
-                       (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps, cj, n_conv, nclaim);
-    } else {
-      FBN_DISPATCH_D_B(adam_claim2_conv_kernel, false, D, g2, p, m, v, cs, (int)n, last,
-                       (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps, cj, n_conv, nclaim);
-    }
-    FBN_CHECK_LAUNCH();
-    return FBN_OK;
-  }
+  const ReplayArgs ra = make_replay(last, consts_table, step, wd, beta2, eps, pend, ring, coef_hist, ring_stride,
+                                    ring_n, decoupled);
+  ClaimSrc cs{nullptr, nullptr, 0, nrows, map, slot_row, nullptr, nullptr, preclaim};
+  cs.lids = lids;
+  cs.skip0 = skip0;
   const dim3 g2((unsigned)((n + 255) / 256));
-  if (decoupled) {
-    FBN_DISPATCH_D_B(adam_claim2_kernel, true, D, g2, p, m, v, cs, (int)n, last, (const AdamConsts*)consts_table,
-                     step, wd, beta2, omb2, eps, ps);
-  } else {
-    FBN_DISPATCH_D_B(adam_claim2_kernel, false, D, g2, p, m, v, cs, (int)n, last, (const AdamConsts*)consts_table,
-                     step, wd, beta2, omb2, eps, ps);
-  }
-  FBN_CHECK_LAUNCH();
-  return FBN_OK;
-}
-
-extern "C" int fbn_adam_flush(float* p, float* m, float* v, long long nrows, int D, int* last, const void* consts_table,
-                              const int* step, float wd, float beta2, float eps, int* pend, const float* ring,
-                              const float* coef_hist, long long ring_stride, int ring_n, int decoupled,
-                              void* stream) {
-  if (nrows <= 0) return FBN_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const float omb2 = (float)(1.0 - (double)beta2);
-  const PendSrc ps = make_pend(pend, ring, coef_hist, ring_stride, ring_n);
-  if (decoupled) {
-    FBN_DISPATCH_D_B(adam_flush_kernel, true, D, group_grid(nrows, D, 16384), p, m, v, nrows, last,
-                     (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps);
-  } else {
-    FBN_DISPATCH_D_B(adam_flush_kernel, false, D, group_grid(nrows, D, 16384), p, m, v, nrows, last,
-                     (const AdamConsts*)consts_table, step, wd, beta2, omb2, eps, ps);
-  }
+  FBN_DISPATCH_D_DW(adam_claim2_kernel, decoupled, D, g2, p, m, v, cs, n, FBN_RA(ra));
   FBN_CHECK_LAUNCH();
   return FBN_OK;
 }

@@ -267,8 +267,8 @@ def test_next_batch_prefetch_bit_identical(hip_device, defer, dups, d, binned, m
     entries of a batch -- the two-pass prefetch gives it to the entry whose tagged pre-claim won
     (no CAS); both runs fold duplicates deterministically (fixed-point sums), as float atomics
     would round in arrival order.  The last step's next_batch is never used: rows prefetched for it are simply up to
-    date early.  binned (d >= 128): the longest-first replay (fbn_adam_prefetch_binned, the default)
-    or adam_prefetch2's 64-entries-per-wave replay."""
+    date early.  binned (d >= 128): the longest-first replay (fbn_adam_prefetch_binned, opt-in:
+    trainer._PF_BINNED is off by default) or adam_prefetch2's 64-entries-per-wave replay, the default."""
     from ctr_recommendation_amd import trainer as trmod
     monkeypatch.setattr(trmod, "_PF_BINNED", binned)
     V, B, L, steps = 40000, 64, 20, 14
