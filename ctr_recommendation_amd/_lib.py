@@ -144,6 +144,11 @@ SIGNATURES = {
     "fbn_eval_pack": (I, [P, P, LL, P, P, P]),
     "fbn_eval_workspace_size": (SZ, [LL]),
     "fbn_eval_reduce": (I, [P, LL, P, SZ, P, P, P]),
+    "fbn_sort_u64_workspace_size": (SZ, [LL]),
+    "fbn_sort_u64": (I, [P, LL, I, P, SZ, P, P]),
+    "fbn_eval_pack_groups": (I, [P, LL, P, P, P]),
+    "fbn_gauc_workspace_size": (SZ, [LL]),
+    "fbn_gauc_reduce": (I, [P, P, LL, P, SZ, P, P, P, P]),
     "fbn_rec_item_cache": (I, [P, P, P, P, P, P, F, I, LL, P, P, I, I, P]),
     "fbn_rec_hist_pool": (I, [P, P, LL, P, P, I, I, I, P]),
     "fbn_rec_fields": (I, [P, P, P, P, P, P, I, P, LL, P, P, P, P, I, P, P, P, I, I, P, P, I, I, I, I, P]),
@@ -181,6 +186,9 @@ SIGNATURES = {
     "fbn_comm_abort": (I, [P]),
     "fbn_comm_watchdog_fired": (I, [P]),
 }
+
+FBN_SORT_TILE = 2048          # include/fibinet.h: keys per workgroup of fbn_sort_u64's passes
+FBN_GAUC_REC_WORDS = 8        # include/fibinet.h: 8-byte words of fbn_gauc_reduce's record
 
 _lib: Optional[ctypes.CDLL] = None
 

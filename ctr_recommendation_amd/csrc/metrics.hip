@@ -28,7 +28,11 @@
 // one log per sample), summed as a fixed-shape tree whose shape depends on n only -- no float atomics.
 //
 // Bad inputs never trap: they set bits of the evaluator's status word (EV_BAD_*), the host raises.
+//
+// The per-group AUC (GAUC) over an arbitrary 32-bit group id is the second half of this file: it
+// sorts (csrc/sort.hip) where the ungrouped reduce counts.
 #include "common.h"
+#include "scan.h"                                // ev_block_excl_scan, scan_top_kernel, fbn_sort_u64
 #include <algorithm>
 
 #define EV_LO_BITS 12
@@ -65,30 +69,6 @@ struct EvalRecord {
 
 static inline int ev_stream_blocks(long long n) {
   return (int)std::min<long long>(EV_LL_MAX, std::max<long long>(1, (n + EV_ELEMS_PER_BLOCK - 1) / EV_ELEMS_PER_BLOCK));
-}
-
-// exclusive prefix sum of v over a workgroup of NW waves (sh: NW words); total = the workgroup's sum
-template <int NW>
-__device__ __forceinline__ uint32_t ev_block_excl_scan(uint32_t v, uint32_t* sh, uint32_t& total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t incl = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  __syncthreads();                               // sh may still be read from the previous scan
-  if (lane == 63) sh[w] = incl;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < NW; ++k) {
-    const uint32_t s = sh[k];
-    if (k < w) base += s;
-    tot += s;
-  }
-  total = tot;
-  return base + incl - v;
 }
 
 // ---------------------------------------------------------------- pack
@@ -393,6 +373,292 @@ extern "C" int fbn_eval_reduce(const uint32_t* keys, long long n, void* ws, size
   fbn_launch(eval_count_kernel, dim3(EV_COUNT_BLOCKS), dim3(EV_COUNT_THREADS), 0, st, (const uint32_t*)hist,
              (const uint32_t*)cursor, (const uint32_t*)negb, (const uint32_t*)list, (const uint32_t*)nlist,
              (const uint16_t*)seg, un, rec);
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}
+
+// ================================================================ grouped AUC (GAUC)
+// The AUC of every group (user) of the samples held, and its three usual averages over the mixed groups
+// (both classes present).  The grouping key is an arbitrary 32-bit id, so the counting of the ungrouped
+// reduce (a table indexed by the key's high bits) has nothing to index: the samples are SORTED by the
+// composite (gid << 31) | key (63 bits; keys are below 2^31) with fbn_sort_u64.  In the sorted array S
+// a group is a segment, a tie a sub-segment, and within a tie the negatives (key bit 0 clear) come first:
+//   c  gauc_compose_kernel   the composite keys
+//      fbn_sort_u64(bits = 63)
+//   s  gauc_scan_*           one two-level scan of (negative, group head) flags packed in a u64:
+//                            N[0 .. n] = negatives before each position, ord[i] = the group's ordinal,
+//                            start[0 .. G] = the groups' first positions, table[g] = {id, U2 = 0}, G
+//   u  gauc_u2_kernel        per group head the class counts from N; per positive the ends of its tie by
+//                            binary search inside its group, 2 * (N[lower] - N[group start]) +
+//                            (N[upper] - N[lower]) added to table[g].U2 -- one u64 atomic per wave when
+//                            the wave's lanes share a group (after the sort they usually do)
+//   f  gauc_part / _final    AUC_g = U2_g / (2 n_pos_g n_neg_g), ONE IEEE double division of exactly
+//                            represented integers (while 2 n_pos_g n_neg_g < 2^53; no fast-math), and the
+//                            three float64 sums over the groups in ascending id order as a fixed-shape
+//                            tree whose shape depends on G only (per-thread index order, an LDS binary
+//                            tree, one thread adding the partials) -- no float atomics.  The group list is
+//                            sorted, so the sums do not depend on the samples' order, on how update()
+//                            split them or on which rank held them.
+// Grids are sized by n and iterate to the device-resident G: no host read anywhere.
+#define EV_BAD_GROUP 0x10000u                    // status bit 16: a group id outside [0, 2^32)
+#define GA_PART_MAX 256                          // workgroups of the fixed tree at most (gauc_final_kernel: one per thread)
+
+struct GaucLayout {
+  size_t comp, sorted, negs, ord, start, bsum, ngroups, partd, partc, sortws, total;
+};
+static inline GaucLayout gauc_layout(long long n) {
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t un = (size_t)n, nb = (un + 255) / 256;
+  GaucLayout L;
+  L.comp = 0;
+  L.sorted = L.comp + al(un * 8);
+  L.negs = L.sorted + al(un * 8);
+  L.ord = L.negs + al((un + 1) * 4);
+  L.start = L.ord + al(un * 4);
+  L.bsum = L.start + al((un + 1) * 4);
+  L.ngroups = L.bsum + al(nb * 8);
+  L.partd = L.ngroups + 256;
+  L.partc = L.partd + al((size_t)GA_PART_MAX * 3 * 8);
+  L.sortws = L.partc + al((size_t)GA_PART_MAX * 3 * 8);
+  L.total = L.sortws + al(fbn_sort_u64_workspace_size(n));
+  return L;
+}
+
+// workgroups of the fixed tree over g groups: a function of g alone (the host sizes the grid with g = n >= G)
+__host__ __device__ static inline uint32_t gauc_blocks(uint32_t g) {
+  const uint32_t b = (g + 255u) / 256u;
+  return b < 1u ? 1u : (b > (uint32_t)GA_PART_MAX ? (uint32_t)GA_PART_MAX : b);
+}
+
+__global__ void __launch_bounds__(256) eval_pack_groups_kernel(const long long* __restrict__ ids, long long n,
+                                                               uint32_t* __restrict__ gids, unsigned* status) {
+  unsigned bad = 0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    long long g = ids[i];
+    if (g < 0) { bad = EV_BAD_GROUP; g = 0; }
+    else if (g > 0xFFFFFFFFll) { bad = EV_BAD_GROUP; g = 0xFFFFFFFFll; }
+    gids[i] = (uint32_t)g;
+  }
+  if (bad) atomicOr(status, bad);
+}
+
+__global__ void __launch_bounds__(256) gauc_compose_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ gids,
+                                                           uint32_t n, uint64_t* __restrict__ comp, unsigned* status) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  uint32_t key = keys[i];
+  if ((key >> 1) > EV_MAX_BITS) {                // a key fbn_eval_pack did not write: counted as 1.0, as the ungrouped reduce does
+    key = (EV_MAX_BITS << 1) | (key & 1u);
+    atomicOr(status, EV_BAD_KEY);
+  }
+  comp[i] = ((uint64_t)gids[i] << 31) | (uint64_t)key;
+}
+
+// (group head << 32) | negative of sorted position i
+__device__ __forceinline__ uint64_t gauc_flags(const uint64_t* __restrict__ S, uint32_t i) {
+  const uint64_t s = S[i];
+  const uint64_t head = (i == 0u || (S[i - 1] >> 31) != (s >> 31)) ? 1ull : 0ull;
+  return (head << 32) | ((s & 1ull) ^ 1ull);
+}
+
+__global__ void __launch_bounds__(256) gauc_scan_sums_kernel(const uint64_t* __restrict__ S, uint32_t n,
+                                                             unsigned long long* __restrict__ bsum) {
+  __shared__ unsigned long long sh[4];
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  unsigned long long total;
+  ev_block_excl_scan<4>((unsigned long long)(i < n ? gauc_flags(S, i) : 0ull), sh, total);
+  if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(256) gauc_scan_apply_kernel(const uint64_t* __restrict__ S, uint32_t n,
+                                                              const unsigned long long* __restrict__ bsum,
+                                                              uint32_t* __restrict__ negs, uint32_t* __restrict__ ord,
+                                                              uint32_t* __restrict__ start, unsigned long long* __restrict__ table,
+                                                              uint32_t* __restrict__ ngroups) {
+  __shared__ unsigned long long sh[4];
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const unsigned long long v = i < n ? gauc_flags(S, i) : 0ull;
+  unsigned long long total;
+  const unsigned long long ex = bsum[blockIdx.x] + ev_block_excl_scan<4>(v, sh, total);
+  if (i >= n) return;
+  const uint32_t neg_before = (uint32_t)ex, head = (uint32_t)(v >> 32);
+  const uint32_t o = (uint32_t)(ex >> 32) + head - 1u;       // position 0 is a head: never below 0
+  negs[i] = neg_before;
+  ord[i] = o;
+  if (head) {
+    start[o] = i;
+    table[4 * (size_t)o + 0] = (unsigned long long)(S[i] >> 31);
+    table[4 * (size_t)o + 1] = 0ull;             // gauc_u2_kernel adds into it
+  }
+  if (i == n - 1u) {
+    negs[n] = neg_before + (uint32_t)(v & 1ull);
+    start[o + 1u] = n;                           // o + 1 = G <= n
+    *ngroups = o + 1u;
+  }
+}
+
+__global__ void __launch_bounds__(256) gauc_u2_kernel(const uint64_t* __restrict__ S, uint32_t n, const uint32_t* __restrict__ negs,
+                                                      const uint32_t* __restrict__ ord, const uint32_t* __restrict__ start,
+                                                      unsigned long long* table) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const bool valid = i < n;
+  uint32_t o = 0u;
+  unsigned long long c = 0ull;
+  if (valid) {
+    const uint64_t s = S[i];
+    o = ord[i];
+    const uint32_t gs = start[o], ge = start[o + 1u];          // gs <= i < ge <= n
+    if (gs == i) {
+      const uint32_t nn = negs[ge] - negs[gs];
+      table[4 * (size_t)o + 2] = (unsigned long long)(ge - gs - nn);
+      table[4 * (size_t)o + 3] = (unsigned long long)nn;
+    }
+    if (s & 1ull) {
+      const uint64_t run = s >> 1;               // group and score: the tie this positive belongs to
+      uint32_t lo = gs, hi = i;                  // first position of the tie: S[i] itself qualifies
+      while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if ((S[mid] >> 1) < run) lo = mid + 1u; else hi = mid;
+      }
+      const uint32_t lower = lo;
+      lo = i + 1u; hi = ge;                      // first position past the tie
+      while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if ((S[mid] >> 1) <= run) lo = mid + 1u; else hi = mid;
+      }
+      const uint32_t nl = negs[lower];
+      c = 2ull * (unsigned long long)(nl - negs[gs]) + (unsigned long long)(negs[lo] - nl);
+    }
+  }
+  // lane 0 is valid whenever any lane is (positions ascend with the lane)
+  const uint32_t o0 = __shfl(o, 0, 64);
+  if (__ballot(valid && o != o0) == 0ull) {      // one group in the wave: one atomic
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d, 64);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&table[4 * (size_t)o0 + 1], c);
+  } else if (c) {
+    atomicAdd(&table[4 * (size_t)o + 1], c);
+  }
+}
+
+// the fixed tree's leaves: workgroup b of gauc_blocks(G), thread t takes groups b * 256 + t, + gauc_blocks(G) * 256, ...
+__global__ void __launch_bounds__(256) gauc_part_kernel(const unsigned long long* __restrict__ table,
+                                                        const uint32_t* __restrict__ ngroups, double* __restrict__ partd,
+                                                        unsigned long long* __restrict__ partc) {
+  __shared__ double rd[3][256];
+  __shared__ unsigned long long rc[3][256];
+  const uint32_t G = *ngroups, vb = gauc_blocks(G), tid = threadIdx.x;
+  if (blockIdx.x >= vb) return;                  // workgroup-uniform
+  double s_n = 0.0, s_1 = 0.0, s_p = 0.0;
+  unsigned long long c_g = 0ull, c_n = 0ull, c_p = 0ull;
+  for (uint32_t g = blockIdx.x * 256u + tid; g < G; g += vb * 256u) {
+    const unsigned long long u2 = table[4 * (size_t)g + 1], np = table[4 * (size_t)g + 2], nn = table[4 * (size_t)g + 3];
+    if (np && nn) {
+      const double auc = (double)u2 / (double)(2ull * np * nn);
+      s_n += __dmul_rn((double)(np + nn), auc);  // the rounded product, then the sum: no contraction
+      s_1 += auc;
+      s_p += __dmul_rn((double)np, auc);
+      c_g += 1ull; c_n += np + nn; c_p += np;
+    }
+  }
+  rd[0][tid] = s_n; rd[1][tid] = s_1; rd[2][tid] = s_p;
+  rc[0][tid] = c_g; rc[1][tid] = c_n; rc[2][tid] = c_p;
+  __syncthreads();
+#pragma unroll
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)tid < s) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { rd[k][tid] += rd[k][tid + s]; rc[k][tid] += rc[k][tid + s]; }
+    }
+    __syncthreads();
+  }
+  if (tid < 3) { partd[blockIdx.x * 3 + tid] = rd[tid][0]; partc[blockIdx.x * 3 + tid] = rc[tid][0]; }
+}
+
+// the partials staged through LDS by one thread each, then added by one thread in index order
+__global__ void __launch_bounds__(GA_PART_MAX) gauc_final_kernel(const uint32_t* __restrict__ ngroups, const double* __restrict__ partd,
+                                                                 const unsigned long long* __restrict__ partc, unsigned long long* out) {
+  __shared__ double sd[3][GA_PART_MAX];
+  __shared__ unsigned long long sc[3][GA_PART_MAX];
+  const uint32_t G = *ngroups, vb = gauc_blocks(G), tid = threadIdx.x;
+  if (tid < vb) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { sd[k][tid] = partd[tid * 3 + k]; sc[k][tid] = partc[tid * 3 + k]; }
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  double d[3] = {0.0, 0.0, 0.0};
+  unsigned long long c[3] = {0ull, 0ull, 0ull};
+  for (uint32_t b = 0; b < vb; ++b)
+    for (int k = 0; k < 3; ++k) { d[k] += sd[k][b]; c[k] += sc[k][b]; }
+  out[0] = (unsigned long long)G;
+  out[1] = c[0]; out[2] = c[1]; out[3] = c[2];
+  out[4] = (unsigned long long)__double_as_longlong(d[0]);
+  out[5] = (unsigned long long)__double_as_longlong(d[1]);
+  out[6] = (unsigned long long)__double_as_longlong(d[2]);
+  out[7] = 0ull;
+}
+
+__global__ void gauc_empty_kernel(unsigned long long* out) {
+  for (int k = 0; k < 8; ++k) out[k] = 0ull;     // 0.0 is all zero bits
+}
+
+extern "C" int fbn_eval_pack_groups(const long long* ids, long long n, uint32_t* gids_out, unsigned* status, void* stream) {
+  if (n <= 0) return FBN_OK;
+  if (!ids || !gids_out || !status) { fbn_set_error("fbn_eval_pack_groups: null argument"); return FBN_ERR_ARG; }
+  if (n >= (1ll << 31)) { fbn_set_error("fbn_eval_pack_groups: n must be below 2^31"); return FBN_ERR_ARG; }
+  const int blocks = (int)std::min<long long>(2048, (n + 255) / 256);
+  fbn_launch(eval_pack_groups_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ids, n, gids_out, status);
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}
+
+extern "C" size_t fbn_gauc_workspace_size(long long n) {
+  if (n < 0) n = 0;
+  return gauc_layout(n).total;
+}
+
+extern "C" int fbn_gauc_reduce(const uint32_t* keys, const uint32_t* gids, long long n, void* ws, size_t ws_bytes,
+                               unsigned long long* table, void* out, unsigned* status, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!out || ((uintptr_t)out & 7)) { fbn_set_error("fbn_gauc_reduce: out must be an 8-B aligned device record"); return FBN_ERR_ARG; }
+  if (n < 0 || n >= (1ll << 31)) { fbn_set_error("fbn_gauc_reduce: need 0 <= n < 2^31"); return FBN_ERR_ARG; }
+  unsigned long long* rec = (unsigned long long*)out;
+  if (n == 0) {
+    fbn_launch(gauc_empty_kernel, dim3(1), dim3(1), 0, st, rec);
+    FBN_CHECK_LAUNCH();
+    return FBN_OK;
+  }
+  if (!keys || !gids || !ws || !table || !status || ((uintptr_t)ws & 15) || ((uintptr_t)table & 7)) {
+    fbn_set_error("fbn_gauc_reduce: keys, gids, status, an 8-B aligned table and a 16-B aligned ws are required");
+    return FBN_ERR_ARG;
+  }
+  const GaucLayout L = gauc_layout(n);
+  if (ws_bytes < L.total) { fbn_set_error("fbn_gauc_reduce: ws smaller than fbn_gauc_workspace_size(n)"); return FBN_ERR_ARG; }
+  char* w = (char*)ws;
+  uint64_t* comp = (uint64_t*)(w + L.comp);
+  uint64_t* sorted = (uint64_t*)(w + L.sorted);
+  uint32_t* negs = (uint32_t*)(w + L.negs);
+  uint32_t* ord = (uint32_t*)(w + L.ord);
+  uint32_t* start = (uint32_t*)(w + L.start);
+  unsigned long long* bsum = (unsigned long long*)(w + L.bsum);
+  uint32_t* ngroups = (uint32_t*)(w + L.ngroups);
+  double* partd = (double*)(w + L.partd);
+  unsigned long long* partc = (unsigned long long*)(w + L.partc);
+  const uint32_t un = (uint32_t)n, nb = (un + 255u) / 256u;
+  fbn_launch(gauc_compose_kernel, dim3(nb), dim3(256), 0, st, keys, gids, un, comp, status);
+  const int rc = fbn_sort_u64(comp, n, 63, w + L.sortws, L.total - L.sortws, sorted, stream);
+  if (rc != FBN_OK) return rc;
+  fbn_launch(gauc_scan_sums_kernel, dim3(nb), dim3(256), 0, st, (const uint64_t*)sorted, un, bsum);
+  fbn_launch(scan_top_kernel<unsigned long long>, dim3(1), dim3(256), 0, st, bsum, nb);
+  fbn_launch(gauc_scan_apply_kernel, dim3(nb), dim3(256), 0, st, (const uint64_t*)sorted, un, (const unsigned long long*)bsum,
+             negs, ord, start, table, ngroups);
+  fbn_launch(gauc_u2_kernel, dim3(nb), dim3(256), 0, st, (const uint64_t*)sorted, un, (const uint32_t*)negs,
+             (const uint32_t*)ord, (const uint32_t*)start, table);
+  fbn_launch(gauc_part_kernel, dim3(gauc_blocks(un)), dim3(256), 0, st, (const unsigned long long*)table,
+             (const uint32_t*)ngroups, partd, partc);
+  fbn_launch(gauc_final_kernel, dim3(1), dim3(GA_PART_MAX), 0, st, (const uint32_t*)ngroups, (const double*)partd,
+             (const unsigned long long*)partc, rec);
   FBN_CHECK_LAUNCH();
   return FBN_OK;
 }

@@ -1,4 +1,4 @@
-"""Validation AUC and log-loss computed on the device, exactly (csrc/metrics.hip, DESIGN.md §15).
+"""Validation AUC and log-loss computed on the device, exactly (csrc/metrics.hip, DESIGN.md §15, §19).
 
 The reference's validation (src/train_fibinet.py:133-146) copies every batch's probabilities to the
 host and runs roc_auc_score / log_loss there (src/utils.py:18-32).  :class:`DeviceMetrics` keeps one
@@ -12,9 +12,15 @@ fixed-shape tree (bitwise reproducible for the same sample sequence).
     for batch, labels in valid_batches:
         m.update(model(batch), labels)          # one launch, no host sync
     out = m.compute()                           # {"auc", "logloss", "n", "n_pos"}: one 40-byte read
+
+``grouped=True`` adds the per-group AUC (GAUC, §19): ``update(..., group_ids=batch["user_id"])`` keeps
+4 more bytes per sample, and compute() also returns the AUC averaged over the groups that hold both
+classes -- exact integer counts per group, float64 sums in ascending id order, so the numbers do not
+depend on the samples' order, on the update sizes or on the rank split.
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, Optional
 
 import numpy as np
@@ -26,14 +32,39 @@ from ._lib import call
 _STATUS = ((1, "a probability is NaN"),
            (2, "a probability lies outside [0, 1]"),
            (4, "a label is neither 0.0 nor 1.0"),
-           (8, "a key was not written by fbn_eval_pack (score bits above 1.0)"))
+           (8, "a key was not written by fbn_eval_pack (score bits above 1.0)"),
+           (1 << 16, "a group id lies outside [0, 2^32)"))
 _MAX_N = (1 << 31) - 1
+_REC = 5                                         # int64 words of the ungrouped record + the status word
+
+
+def gauc_from_table(table: Dict) -> Dict:
+    """The three GAUC averages from the integer group table (``group_table()``'s dict, tensors or
+    arrays), on the host in float64: ``AUC_g = u2 / (2 n_pos n_neg)`` per mixed group (both classes
+    present), then ``gauc`` weighted by the group's samples, ``gauc_macro`` unweighted, ``gauc_clicks``
+    weighted by its positives, each numerator summed with ``math.fsum``.  NaN without a mixed group.
+    The reference for the device's sums, and the starting point for any other weighting."""
+    def col(k):
+        v = table[k]
+        return (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.int64)
+    u2, n_pos, n_neg = col("u2"), col("n_pos"), col("n_neg")
+    mixed = (n_pos > 0) & (n_neg > 0)
+    u2, n_pos, n_neg = u2[mixed], n_pos[mixed], n_neg[mixed]
+    n = n_pos + n_neg
+    auc = u2.astype(np.float64) / (2 * n_pos * n_neg).astype(np.float64)     # exact integers: one IEEE division
+    n_mixed, n_groups_mixed, clicks = int(n.sum()), int(mixed.sum()), int(n_pos.sum())
+    nan = float("nan")
+    return {"gauc": math.fsum(n.astype(np.float64) * auc) / n_mixed if n_groups_mixed else nan,
+            "gauc_macro": math.fsum(auc) / n_groups_mixed if n_groups_mixed else nan,
+            "gauc_clicks": math.fsum(n_pos.astype(np.float64) * auc) / clicks if n_groups_mixed else nan,
+            "n_groups": int(len(mixed)), "n_groups_mixed": n_groups_mixed, "n_mixed": n_mixed}
 
 
 class DeviceMetrics:
-    """Streaming exact ROC-AUC + log-loss of up to ``capacity`` samples held as keys on ``device``."""
+    """Streaming exact ROC-AUC + log-loss of up to ``capacity`` samples held as keys on ``device``;
+    ``grouped``: also their group ids, for the per-group AUC."""
 
-    def __init__(self, capacity: int, device=None):
+    def __init__(self, capacity: int, device=None, grouped: bool = False):
         self.device = torch.device(device if device is not None else "cuda")
         if self.device.type != "cuda":
             raise RuntimeError("DeviceMetrics runs on a HIP device only (no CPU fallback)")
@@ -41,25 +72,46 @@ class DeviceMetrics:
         if not 0 <= capacity <= _MAX_N:
             raise ValueError(f"capacity must be in [0, 2^31), not {capacity}")
         self.capacity = capacity
+        self.grouped = bool(grouped)
         # keys are below 2^31 (score bits < 2^30), so the int32 view orders as the uint32 keys do
         self.keys = torch.empty(max(1, capacity), dtype=torch.int32, device=self.device)
-        # {u64 U2, u64 n_pos, u64 n_neg, f64 logloss_sum} + the status word: read back in one copy
-        self.rec = torch.zeros(5, dtype=torch.int64, device=self.device)
+        # uint32 group ids (the int32 view holds their bits)
+        self.gids = torch.empty(max(1, capacity), dtype=torch.int32, device=self.device) if self.grouped else None
+        # {u64 U2, u64 n_pos, u64 n_neg, f64 logloss_sum} + the status word (+ the grouped record):
+        # read back in one copy
+        self.rec = self._new_rec()
         self.count = 0
         self._ws: Optional[torch.Tensor] = None
+        self._gws: Optional[torch.Tensor] = None
+        self._table: Optional[torch.Tensor] = None         # [n][4] int64 of the last grouped reduce
+        self._table_rows: Optional[int] = None             # its G; None: stale
+
+    def _new_rec(self) -> torch.Tensor:
+        return torch.zeros(_REC + (_lib.FBN_GAUC_REC_WORDS if self.grouped else 0), dtype=torch.int64, device=self.device)
 
     # ------------------------------------------------------------------ streaming
     def reset(self) -> None:
         self.count = 0
         self.rec.zero_()
+        self._table_rows = None
 
-    def update(self, probs: torch.Tensor, labels: torch.Tensor) -> None:
-        """Append a batch: one pack launch, no host sync (bad values surface in compute())."""
+    def update(self, probs: torch.Tensor, labels: torch.Tensor, group_ids: Optional[torch.Tensor] = None) -> None:
+        """Append a batch: one pack launch (two when grouped), no host sync (bad values surface in
+        compute()).  group_ids: one integer id in [0, 2^32) per sample, of any integer dtype or a float
+        tensor holding integers; required by a grouped instance, refused by any other."""
         _lib.require_hip(probs, "probs")
         _lib.require_hip(labels, "labels")
         n = probs.numel()
         if labels.numel() != n:
             raise ValueError(f"probs has {n} elements, labels {labels.numel()}")
+        if self.grouped:
+            if group_ids is None:
+                raise ValueError("a grouped DeviceMetrics needs group_ids with every update()")
+            _lib.require_hip(group_ids, "group_ids")
+            if group_ids.numel() != n:
+                raise ValueError(f"probs has {n} elements, group_ids {group_ids.numel()}")
+        elif group_ids is not None:
+            raise ValueError("group_ids given to a DeviceMetrics built without grouped=True")
         if self.count + n > self.capacity:
             raise ValueError(f"DeviceMetrics capacity {self.capacity} exceeded ({self.count} held + {n} new)")
         if n == 0:
@@ -69,7 +121,12 @@ class DeviceMetrics:
         with torch.cuda.device(self.device):
             call("fbn_eval_pack", p.data_ptr(), y.data_ptr(), n, self.keys.data_ptr() + 4 * self.count,
                  self.rec.data_ptr() + 32, _lib.stream_handle(self.device))
+            if self.grouped:
+                g = group_ids.detach().reshape(-1).to(torch.int64).contiguous()
+                call("fbn_eval_pack_groups", g.data_ptr(), n, self.gids.data_ptr() + 4 * self.count,
+                     self.rec.data_ptr() + 32, _lib.stream_handle(self.device))
         self.count += n
+        self._table_rows = None
 
     # ------------------------------------------------------------------ result
     def _workspace(self, n: int) -> torch.Tensor:
@@ -79,12 +136,27 @@ class DeviceMetrics:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
 
-    def _reduce(self, keys: torch.Tensor, n: int, rec: torch.Tensor) -> Dict:
+    def _group_buffers(self, n: int):
+        need = int(call("fbn_gauc_workspace_size", n))
+        if self._gws is None or self._gws.numel() < need:
+            self._gws = None
+            self._gws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if self._table is None or self._table.shape[0] < n:
+            self._table = None
+            self._table = torch.empty((max(1, n), 4), dtype=torch.int64, device=self.device)
+        return self._gws, self._table
+
+    def _reduce(self, keys: torch.Tensor, n: int, rec: torch.Tensor, gids: Optional[torch.Tensor] = None) -> Dict:
         ws = self._workspace(n)
         with torch.cuda.device(self.device):
             call("fbn_eval_reduce", keys.data_ptr(), n, ws.data_ptr(), ws.numel(), rec.data_ptr(),
                  rec.data_ptr() + 32, _lib.stream_handle(self.device))
-        host = rec.cpu().numpy()                 # the one device-to-host read: record + status
+            if self.grouped:
+                gws, table = self._group_buffers(n)
+                call("fbn_gauc_reduce", keys.data_ptr(), gids.data_ptr(), n, gws.data_ptr(), gws.numel(),
+                     table.data_ptr(), rec.data_ptr() + 8 * _REC, rec.data_ptr() + 32, _lib.stream_handle(self.device))
+        self._table_rows = None
+        host = rec.cpu().numpy()                 # the one device-to-host read: record(s) + status
         status = int(host[4]) & 0xFFFFFFFF
         if status:
             raise ValueError("DeviceMetrics: " + "; ".join(msg for bit, msg in _STATUS if status & bit))
@@ -92,17 +164,42 @@ class DeviceMetrics:
         ll_sum = float(host[3:4].view(np.float64)[0])
         total = n_pos + n_neg
         auc = 0.5 if n_pos == 0 or n_neg == 0 else u2 / (2 * n_pos * n_neg)
-        return {"auc": auc, "logloss": ll_sum / total if total else float("nan"), "n": total, "n_pos": n_pos}
+        out = {"auc": auc, "logloss": ll_sum / total if total else float("nan"), "n": total, "n_pos": n_pos}
+        if self.grouped:
+            g = host[_REC:]
+            n_groups, n_groups_mixed, n_mixed, clicks = int(g[0]), int(g[1]), int(g[2]), int(g[3])
+            s_n, s_1, s_p = (float(v) for v in g[4:7].view(np.float64))
+            nan = float("nan")
+            out.update(gauc=s_n / n_mixed if n_groups_mixed else nan,
+                       gauc_macro=s_1 / n_groups_mixed if n_groups_mixed else nan,
+                       gauc_clicks=s_p / clicks if n_groups_mixed else nan,
+                       n_groups=n_groups, n_groups_mixed=n_groups_mixed, n_mixed=n_mixed)
+            self._table_rows = n_groups
+        return out
+
+    def group_table(self) -> Dict[str, torch.Tensor]:
+        """{"group", "u2", "n_pos", "n_neg"}: int64 device tensors of length G, one entry per group in
+        ascending id order -- the exact integers behind the last compute() (run now, over the samples
+        held, if there was none since the last update()).  An analysis call: it reads G from the host."""
+        if not self.grouped:
+            raise ValueError("group_table() needs a DeviceMetrics built with grouped=True")
+        if self._table_rows is None:
+            self.compute()
+        t = self._table[:self._table_rows]
+        return {"group": t[:, 0].clone(), "u2": t[:, 1].clone(), "n_pos": t[:, 2].clone(), "n_neg": t[:, 3].clone()}
 
     def compute(self, group=None, stage_on_cpu: bool = False) -> Dict:
-        """{"auc", "logloss", "n", "n_pos"} of the samples held (they stay: compute() can be repeated).
+        """{"auc", "logloss", "n", "n_pos"} of the samples held (they stay: compute() can be repeated);
+        grouped: plus {"gauc", "gauc_macro", "gauc_clicks", "n_groups", "n_groups_mixed", "n_mixed"}
+        (the averages are NaN when no group holds both classes).
 
-        group: a torch.distributed process group -- collective; every rank's keys are all-gathered
-        (4 B per sample, padded to the largest count) and reduced on every rank, in rank-major order:
-        key order does not enter the AUC and the log-loss tree sees the same sequence everywhere, so
-        all ranks return identical numbers.  stage_on_cpu: gather through host tensors (gloo)."""
+        group: a torch.distributed process group -- collective; every rank's keys (and group ids) are
+        all-gathered (4 B each per sample, padded to the largest count) and reduced on every rank, in
+        rank-major order: key order does not enter the AUC or the grouped numbers, and the log-loss
+        tree sees the same sequence everywhere, so all ranks return identical numbers.
+        stage_on_cpu: gather through host tensors (gloo)."""
         if group is None:
-            return self._reduce(self.keys, self.count, self.rec)
+            return self._reduce(self.keys, self.count, self.rec, self.gids)
         import torch.distributed as dist
         world = dist.get_world_size(group)
         counts = [None] * world
@@ -110,21 +207,28 @@ class DeviceMetrics:
         maxc, total = max(counts), sum(counts)
         if total > _MAX_N:
             raise ValueError(f"{total} samples over the group: the device reduce needs n < 2^31")
-        # one buffer per rank: its keys, padding, and its status word in the last slot
-        send = torch.zeros(maxc + 1, dtype=torch.int32, device=self.device)
+        # one buffer per rank: its keys, padding, (its group ids, padding,) and its status word in the last slot
+        cols = 2 if self.grouped else 1
+        width = cols * maxc + 1
+        send = torch.zeros(width, dtype=torch.int32, device=self.device)
         send[:self.count] = self.keys[:self.count]
-        send[maxc:] = self.rec.view(torch.int32)[8:9]
+        if self.grouped:
+            send[maxc:maxc + self.count] = self.gids[:self.count]
+        send[width - 1:] = self.rec.view(torch.int32)[8:9]
         if stage_on_cpu:
-            parts = [torch.empty(maxc + 1, dtype=torch.int32) for _ in range(world)]
+            parts = [torch.empty(width, dtype=torch.int32) for _ in range(world)]
             dist.all_gather(parts, send.cpu(), group=group)
             got = torch.stack(parts).to(self.device)
         else:
-            got = torch.empty((world, maxc + 1), dtype=torch.int32, device=self.device)
+            got = torch.empty((world, width), dtype=torch.int32, device=self.device)
             dist.all_gather_into_tensor(got.view(-1), send, group=group)
         keys = torch.cat([got[r, :counts[r]] for r in range(world)]) if total else self.keys[:0]
-        rec = torch.zeros(5, dtype=torch.int64, device=self.device)
-        status = got[0, maxc:].clone()
+        gids = None
+        if self.grouped:
+            gids = (torch.cat([got[r, maxc:maxc + counts[r]] for r in range(world)]) if total else self.gids[:0]).contiguous()
+        rec = self._new_rec()
+        status = got[0, width - 1:].clone()
         for r in range(1, world):
-            status |= got[r, maxc:]
+            status |= got[r, width - 1:]
         rec.view(torch.int32)[8:9] = status
-        return self._reduce(keys.contiguous(), total, rec)
+        return self._reduce(keys.contiguous(), total, rec, gids)

@@ -64,7 +64,8 @@ def set_seed(seed: int) -> None:
 def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoint: Optional[str] = None,
         log=print, overrides: Optional[Dict] = None) -> Dict:
     """Train as src/train_fibinet.py does; returns {"best_auc", "history": [(epoch, loss, auc)],
-    "valid_logloss": [per epoch], "trainer"}."""
+    "valid_logloss": [per epoch], "trainer"}; with the model-config key ``valid_group_by`` (a batch
+    column, e.g. user_id) also "valid_gauc": [per epoch] and a `` | Valid GAUC: `` field on the epoch line."""
     import torch.distributed as dist
 
     from .loader import make_loaders
@@ -97,6 +98,8 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
                              init_state=init, seed=seed, table_adam=str(model_cfg.get("table_adam", "lazy")))
     del init
     best_auc, history, valid_logloss = 0.0, [], []
+    group_by = model_cfg.get("valid_group_by")            # e.g. user_id: also report the per-group AUC
+    valid_gauc = []
     ckpt = checkpoint or os.path.join("..", "checkpoints", "FiBiNET_best.pth")
     for epoch in range(n_epochs):
         t0 = time.perf_counter()
@@ -124,16 +127,21 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
         dt = time.perf_counter() - t0
         # validation (:133-146): eval-mode probabilities of the whole split, packed and counted on the
         # device (metrics.DeviceMetrics: the exact AUC, the double utils.compute_auc returns on them)
-        ev = trainer.evaluate(valid_loader)
+        ev = trainer.evaluate(valid_loader, group_by=str(group_by)) if group_by else trainer.evaluate(valid_loader)
         valid_loader.check(world=world)
         auc = logloss = None
         if len(valid_loader):
             auc, logloss = float(ev["auc"]), float(ev["logloss"])
         history.append((epoch + 1, avg_loss, auc))
         valid_logloss.append(logloss)
-        log0(f"Epoch {epoch + 1} | Train Loss: {avg_loss:.4f} | Valid AUC: {auc if auc is None else round(auc, 4)} | "
-             f"{steps * train_loader.batch_size / dt:.0f} samples/s | "
-             f"Valid LogLoss: {logloss if logloss is None else round(logloss, 4)}")
+        line = (f"Epoch {epoch + 1} | Train Loss: {avg_loss:.4f} | Valid AUC: {auc if auc is None else round(auc, 4)} | "
+                f"{steps * train_loader.batch_size / dt:.0f} samples/s | "
+                f"Valid LogLoss: {logloss if logloss is None else round(logloss, 4)}")
+        if group_by:
+            gauc = float(ev["gauc"]) if len(valid_loader) else None
+            valid_gauc.append(gauc)
+            line += f" | Valid GAUC: {gauc if gauc is None else f'{gauc:.4f}'}"
+        log0(line)
         if auc is not None and auc > best_auc:
             best_auc = auc
             sd = trainer.state_dict()                     # collective at N > 1 (table on rank 0 only)
@@ -142,7 +150,10 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
                 torch.save(sd, ckpt)
                 log0(f"New best FiBiNET AUC; saved to {ckpt}")
     log0(f"Done. Best AUC: {best_auc:.4f}")
-    return {"best_auc": best_auc, "history": history, "valid_logloss": valid_logloss, "trainer": trainer}
+    out = {"best_auc": best_auc, "history": history, "valid_logloss": valid_logloss, "trainer": trainer}
+    if group_by:
+        out["valid_gauc"] = valid_gauc
+    return out
 
 
 def main(argv=None):

@@ -1222,7 +1222,7 @@ class FiBiNETTrainer:
         return (a["logits"] if logits else a["probs"]).clone()
 
     @torch.no_grad()
-    def evaluate(self, loader_or_batches, metrics=None) -> Dict:
+    def evaluate(self, loader_or_batches, metrics=None, group_by: Optional[str] = None) -> Dict:
         """Validation metrics of (batch, labels) pairs without a per-batch host transfer: predict()'s
         eval-mode forward per batch, its probabilities packed straight into a metrics.DeviceMetrics
         (one launch per batch), then one exact device reduce and one 40-byte read.  Returns
@@ -1230,8 +1230,12 @@ class FiBiNETTrainer:
         concatenated predict() outputs (src/train_fibinet.py:133-146).  N > 1: collective exactly as
         predict() is (a rank with an empty slice still joins) plus the key all-gather -- every rank
         returns the global numbers.  metrics: a DeviceMetrics to fill (reset first; its capacity must
-        hold this rank's samples); default: one sized for the input, kept for the next call."""
+        hold this rank's samples); default: one sized for the input, kept for the next call.
+        group_by: a batch column of integer ids (e.g. "user_id"): the metrics are grouped by it and the
+        result also holds {"gauc", "gauc_macro", "gauc_clicks", "n_groups", "n_groups_mixed", "n_mixed"}
+        (metrics.DeviceMetrics(grouped=True)); KeyError if a batch lacks the column."""
         from .metrics import DeviceMetrics
+        grouped = group_by is not None
         if metrics is None:
             ds = getattr(loader_or_batches, "ds", None)
             if ds is not None:                                # DeviceLoader: this rank's share of every batch
@@ -1240,14 +1244,15 @@ class FiBiNETTrainer:
                 loader_or_batches = list(loader_or_batches)
                 need = sum(int(y.numel()) for _, y in loader_or_batches)
             metrics = self._eval_metrics
-            if metrics is None or metrics.capacity < need:
+            if metrics is None or metrics.capacity < need or metrics.grouped != grouped:
                 self._eval_metrics = None
-                metrics = self._eval_metrics = DeviceMetrics(need, self.device)
+                metrics = self._eval_metrics = DeviceMetrics(need, self.device, grouped=grouped)
         metrics.reset()
         for batch, labels in loader_or_batches:
+            ids = batch[group_by] if grouped else None
             probs = self.predict(batch)
             if probs.numel():
-                metrics.update(probs, labels)
+                metrics.update(probs, labels, group_ids=ids)
         if self.world > 1:
             group = self.group if self.group is not None else dist.group.WORLD
             return metrics.compute(group=group, stage_on_cpu=self.stage_on_cpu)

@@ -668,6 +668,46 @@ size_t fbn_eval_workspace_size(long long n);
 int fbn_eval_reduce(const uint32_t* keys, long long n, void* ws, size_t ws_bytes, void* out, unsigned* status,
                     void* stream);
 
+/* ---------------------------------------------------------------- device sort (64-bit keys)
+ * The reference has no device sort (its only ordering is the host argsort inside roc_auc_score,
+ * src/utils.py:18-27).  fbn_sort_u64: out[0 .. n) = in[0 .. n) ascending by the low `bits` bits
+ * (1 .. 64); the bits above them must be equal across the keys (they are carried, not compared: the
+ * last pass's digit may reach into them).  LSD radix, 8 bits per pass, ceil(bits / 8) passes: the
+ * host picks bits, so the launch sequence is known without a device round trip.  in is not modified
+ * and must not overlap out; 0 <= n < 2^31 (else FBN_ERR_ARG, checked on the host before any device
+ * work); n == 0 launches nothing.  ws: >= fbn_sort_u64_workspace_size(n) bytes (host-only query),
+ * 16-B aligned.  No host synchronisation, no allocation.  FBN_SORT_TILE: keys per workgroup. */
+#define FBN_SORT_TILE 2048
+size_t fbn_sort_u64_workspace_size(long long n);
+int fbn_sort_u64(const uint64_t* in, long long n, int bits, void* ws, size_t ws_bytes, uint64_t* out, void* stream);
+
+/* ---------------------------------------------------------------- device metrics: grouped AUC (GAUC)
+ * The reference has no per-user metric: this replaces the host-side grouping a user writes around its
+ * validation loop (every batch's probabilities, labels and user ids copied to the host as in
+ * src/train_fibinet.py:133-146, then roc_auc_score of src/utils.py:18-32 per user) by a device sort
+ * and integer counting.  A group is the set of samples with one id g in [0, 2^32); n_pos_g / n_neg_g
+ * its class counts; U2_g fbn_eval_reduce's U2 restricted to the group, over the same keys; a group is
+ * mixed when both counts are non-zero, and only mixed groups enter the averages (DIN's convention).
+ * fbn_eval_pack_groups: n ids -> uint32 at gids_out (the caller passes gids + count); an id outside
+ * [0, 2^32) sets bit 16 of *status and is packed clamped -- nothing traps; no host sync.
+ * fbn_gauc_reduce over keys[0 .. n), gids[0 .. n), 0 <= n < 2^31:
+ *   table [n][4] uint64 {id, U2, n_pos, n_neg}: the first G rows are written, in ascending id order;
+ *   out = device record of FBN_GAUC_REC_WORDS 8-byte words (8-B aligned):
+ *     0 u64 G   1 u64 mixed groups   2 u64 samples in mixed groups   3 u64 positives in mixed groups
+ *     4 f64 sum n_g AUC_g   5 f64 sum AUC_g   6 f64 sum n_pos_g AUC_g   7 u64 0      (over the mixed groups)
+ *   AUC_g = U2_g / (2 n_pos_g n_neg_g) is one IEEE double division of exact integers on the device: the
+ *   double utils.compute_auc returns on the group's samples while 2 n_pos_g n_neg_g < 2^53.  The three
+ *   sums are float64, added over the groups in ascending id order as a fixed-shape tree whose shape
+ *   depends on G only (no float atomics): bitwise independent of the samples' order.  n == 0 writes
+ *   zeros.  A key above (0x3F800000 << 1) | 1 is counted as 1.0 and sets bit 3 of *status.
+ *   ws: >= fbn_gauc_workspace_size(n) bytes (host-only query), 16-B aligned.  Null pointers, n >= 2^31
+ *   and a small or misaligned ws return FBN_ERR_ARG before any device work.  No host sync. */
+#define FBN_GAUC_REC_WORDS 8
+int fbn_eval_pack_groups(const long long* ids, long long n, uint32_t* gids_out, unsigned* status, void* stream);
+size_t fbn_gauc_workspace_size(long long n);
+int fbn_gauc_reduce(const uint32_t* keys, const uint32_t* gids, long long n, void* ws, size_t ws_bytes,
+                    unsigned long long* table, void* out, unsigned* status, void* stream);
+
 /* ---------------------------------------------------------------- serving: catalogue scoring + top-K
  * Replaces the per-row scoring loop of src/Prediction.py:106-113 when the rows are the U x M pairs
  * (user u, catalogue item m): the field construction of src/model_fibinet.py:152-188 is split into
