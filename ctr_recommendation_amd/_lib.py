@@ -149,6 +149,8 @@ SIGNATURES = {
     "fbn_eval_pack_groups": (I, [P, LL, P, P, P]),
     "fbn_gauc_workspace_size": (SZ, [LL]),
     "fbn_gauc_reduce": (I, [P, P, LL, P, SZ, P, P, P, P]),
+    "fbn_calib_workspace_size": (SZ, [LL]),
+    "fbn_calib_reduce": (I, [P, LL, I, P, SZ, P, P, P]),
     "fbn_rec_item_cache": (I, [P, P, P, P, P, P, F, I, LL, P, P, I, I, P]),
     "fbn_rec_hist_pool": (I, [P, P, LL, P, P, I, I, I, P]),
     "fbn_rec_fields": (I, [P, P, P, P, P, P, I, P, LL, P, P, P, P, I, P, P, P, I, I, P, P, I, I, I, I, P]),
@@ -189,6 +191,8 @@ SIGNATURES = {
 
 FBN_SORT_TILE = 2048          # include/fibinet.h: keys per workgroup of fbn_sort_u64's passes
 FBN_GAUC_REC_WORDS = 8        # include/fibinet.h: 8-byte words of fbn_gauc_reduce's record
+FBN_CALIB_MAX_BINS = 1024     # include/fibinet.h: bins of fbn_calib_reduce at most
+FBN_CALIB_BIN_WORDS = 8       # include/fibinet.h: 8-byte words per bin of its table
 
 _lib: Optional[ctypes.CDLL] = None
 

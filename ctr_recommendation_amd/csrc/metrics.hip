@@ -30,7 +30,8 @@
 // Bad inputs never trap: they set bits of the evaluator's status word (EV_BAD_*), the host raises.
 //
 // The per-group AUC (GAUC) over an arbitrary 32-bit group id is the second half of this file: it
-// sorts (csrc/sort.hip) where the ungrouped reduce counts.
+// sorts (csrc/sort.hip) where the ungrouped reduce counts.  The calibration table (reliability bins,
+// the sums behind ECE / PCOC / Brier) is the third part: one sort of the keys and one prefix sum.
 #include "common.h"
 #include "scan.h"                                // ev_block_excl_scan, scan_top_kernel, fbn_sort_u64
 #include <algorithm>
@@ -659,6 +660,203 @@ extern "C" int fbn_gauc_reduce(const uint32_t* keys, const uint32_t* gids, long 
              (const uint32_t*)ngroups, partd, partc);
   fbn_launch(gauc_final_kernel, dim3(1), dim3(GA_PART_MAX), 0, st, (const uint32_t*)ngroups, (const double*)partd,
              (const unsigned long long*)partc, rec);
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}
+
+// ================================================================ calibration
+// The reliability table of the samples held, in two binnings of B bins each: equal width (bin =
+// min(B - 1, floor((double)p * B))) and equal mass (bin b = the sorted ranks [floor(b n / B),
+// floor((b + 1) n / B))).  Both binnings are monotone in the key, so after ONE sort of the keys a bin of
+// either is a rank range [lo, hi) and every bin sum is a difference of one prefix sum at two ranks:
+//   w  calib_widen_kernel    the keys as u64 (a key above bits(1.0) clamped and flagged, as above)
+//      fbn_sort_u64(bits = 31)
+//   s  calib_sums_kernel     per 256 sorted samples the sums of {y, fx, y fx, fx2}, fx = rint(p 2^32) and
+//                            fx2 = rint(p p 2^32) through exact float64 products; scan_top_kernel turns
+//                            each of the four columns into its exclusive prefix over the blocks
+//   b  calib_bound_kernel    one workgroup per boundary (2 (B + 1) of them): its rank -- floor(b n / B),
+//                            or the first rank whose width bin is >= b by binary search -- and the prefix
+//                            there = the block's prefix + the samples of the block before the rank
+//   t  calib_table_kernel    one thread per bin and plane: the differences, the first and last score of
+//                            the range, and the trailing status word
+// Every sum is a u64 integer sum (fx, fx2 <= 2^32 and n < 2^31: below 2^63), so nothing depends on any
+// order; the sort makes the tie split (negatives first) canonical.  No atomics except the status bit.
+#define FBN_CALIB_MAX_BINS 1024                  // include/fibinet.h publishes the same two values
+#define FBN_CALIB_BIN_WORDS 8
+#define CA_REC 4                                 // prefix columns: y, fx, y * fx, fx2
+#define CA_BND 5                                 // words per boundary: rank + the four prefixes
+
+struct CalibLayout {
+  size_t wide, sorted, bsum, bnd, sortws, total;
+  uint32_t nb1;                                  // blocks of 256 samples + 1 (the prefix at rank n has a block too)
+};
+static inline CalibLayout calib_layout(long long n) {
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t un = (size_t)n;
+  CalibLayout L;
+  L.nb1 = (uint32_t)((un + 255) / 256 + 1);
+  L.wide = 0;
+  L.sorted = L.wide + al(un * 8);
+  L.bsum = L.sorted + al(un * 8);
+  L.bnd = L.bsum + al((size_t)CA_REC * L.nb1 * 8);
+  L.sortws = L.bnd + al((size_t)2 * (FBN_CALIB_MAX_BINS + 1) * CA_BND * 8);
+  L.total = L.sortws + al(fbn_sort_u64_workspace_size(n));
+  return L;
+}
+
+__global__ void __launch_bounds__(256) calib_widen_kernel(const uint32_t* __restrict__ keys, uint32_t n,
+                                                          uint64_t* __restrict__ wide, unsigned* status) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  uint32_t key = keys[i];
+  if ((key >> 1) > EV_MAX_BITS) {                // a key fbn_eval_pack did not write: counted as 1.0
+    key = (EV_MAX_BITS << 1) | (key & 1u);
+    atomicOr(status, EV_BAD_KEY);
+  }
+  wide[i] = (uint64_t)key;
+}
+
+// {y, fx, y * fx, fx2} of a sorted key: p * 2^32 and p * p * 2^32 are exact in float64 (24- and 48-bit
+// significands), rint rounds half to even
+__device__ __forceinline__ void calib_record(uint64_t s, unsigned long long* r) {
+  const double p = (double)__uint_as_float((uint32_t)(s >> 1));
+  const unsigned long long y = s & 1ull;
+  const unsigned long long fx = (unsigned long long)rint(p * 4294967296.0);
+  r[0] = y;
+  r[1] = fx;
+  r[2] = y ? fx : 0ull;
+  r[3] = (unsigned long long)rint(p * p * 4294967296.0);
+}
+
+// the sums of the samples [lo, hi) (hi - lo <= 256) in every thread
+__device__ __forceinline__ void calib_block_sums(const uint64_t* __restrict__ S, uint32_t lo, uint32_t hi,
+                                                 unsigned long long* sh, unsigned long long* tot) {
+  const uint32_t i = lo + threadIdx.x;
+  unsigned long long r[CA_REC] = {0ull, 0ull, 0ull, 0ull};
+  if (i < hi) calib_record(S[i], r);
+#pragma unroll
+  for (int k = 0; k < CA_REC; ++k) ev_block_excl_scan<4>(r[k], sh, tot[k]);
+}
+
+// grid: nb1 workgroups; the last one (and the tail of the one before) holds no sample
+__global__ void __launch_bounds__(256) calib_sums_kernel(const uint64_t* __restrict__ S, uint32_t n, uint32_t nb1,
+                                                         unsigned long long* __restrict__ bsum) {
+  __shared__ unsigned long long sh[4];
+  const uint32_t lo = blockIdx.x * 256u;         // the last workgroup's lo is >= n: an empty range
+  unsigned long long tot[CA_REC];
+  calib_block_sums(S, lo, lo + 256u < n ? lo + 256u : n, sh, tot);   // n < 2^31: lo + 256 does not wrap
+#pragma unroll
+  for (int k = 0; k < CA_REC; ++k)
+    if (threadIdx.x == (unsigned)k) bsum[(size_t)k * nb1 + blockIdx.x] = tot[k];
+}
+
+// the width bin of a sorted key is >= b  (1 <= b <= B - 1, so the min(B - 1, .) of the rule does not enter)
+__device__ __forceinline__ bool calib_width_ge(uint64_t s, int b, int B) {
+  return (int)floor((double)__uint_as_float((uint32_t)(s >> 1)) * (double)B) >= b;
+}
+
+// workgroup (plane, b), b = 0 .. B: plane 0 equal width, plane 1 equal mass
+__global__ void __launch_bounds__(256) calib_bound_kernel(const uint64_t* __restrict__ S, uint32_t n, int B, uint32_t nb1,
+                                                          const unsigned long long* __restrict__ bsum,
+                                                          unsigned long long* __restrict__ bnd) {
+  __shared__ unsigned long long sh[4];
+  __shared__ uint32_t rank;
+  const int plane = blockIdx.x / (B + 1), b = blockIdx.x % (B + 1);
+  if (threadIdx.x == 0) {
+    uint32_t r;
+    if (plane == 1) r = (uint32_t)(((unsigned long long)b * n) / (unsigned long long)B);
+    else if (b == 0) r = 0u;
+    else if (b == B) r = n;
+    else {
+      uint32_t lo = 0u, hi = n;                  // the first rank whose width bin is >= b (n: none)
+      while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (calib_width_ge(S[mid], b, B)) hi = mid; else lo = mid + 1u;
+      }
+      r = lo;
+    }
+    rank = r;
+  }
+  __syncthreads();
+  const uint32_t r = rank, blk = r >> 8;         // r <= n: blk <= nb1 - 1, and the samples [blk * 256, r) exist
+  unsigned long long tot[CA_REC];
+  calib_block_sums(S, blk * 256u, r, sh, tot);
+  unsigned long long* o = bnd + (size_t)blockIdx.x * CA_BND;
+  if (threadIdx.x == 0) o[0] = (unsigned long long)r;
+#pragma unroll
+  for (int k = 0; k < CA_REC; ++k)
+    if (threadIdx.x == (unsigned)k) o[1 + k] = bsum[(size_t)k * nb1 + blk] + tot[k];
+}
+
+__global__ void __launch_bounds__(256) calib_table_kernel(const uint64_t* __restrict__ S, int B,
+                                                          const unsigned long long* __restrict__ bnd,
+                                                          const unsigned* __restrict__ status, uint64_t* __restrict__ out) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t == 0) out[(size_t)2 * B * FBN_CALIB_BIN_WORDS] = (uint64_t)*status;
+  if (t >= 2 * B) return;
+  const int plane = t / B, b = t % B;
+  const unsigned long long* lo = bnd + ((size_t)plane * (B + 1) + b) * CA_BND;
+  const unsigned long long* hi = lo + CA_BND;
+  uint64_t* o = out + (size_t)t * FBN_CALIB_BIN_WORDS;
+  const uint32_t r0 = (uint32_t)lo[0], r1 = (uint32_t)hi[0];     // r0 <= r1: both boundary rules are monotone in b
+  o[0] = (uint64_t)(r1 - r0);
+#pragma unroll
+  for (int k = 0; k < CA_REC; ++k) o[1 + k] = hi[1 + k] - lo[1 + k];
+  o[5] = r1 > r0 ? ((S[r0] >> 1) & 0xFFFFFFFFull) | (((S[r1 - 1u] >> 1) & 0xFFFFFFFFull) << 32) : 0ull;
+  o[6] = 0ull;
+  o[7] = 0ull;
+}
+
+__global__ void __launch_bounds__(256) calib_empty_kernel(int words, const unsigned* __restrict__ status,
+                                                          uint64_t* __restrict__ out) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t < words) out[t] = 0ull;
+  else if (t == words) out[t] = (uint64_t)*status;
+}
+
+extern "C" size_t fbn_calib_workspace_size(long long n) {
+  if (n < 0) n = 0;
+  return calib_layout(n).total;
+}
+
+extern "C" int fbn_calib_reduce(const uint32_t* keys, long long n, int bins, void* ws, size_t ws_bytes, uint64_t* out,
+                                unsigned* status, void* stream) {
+  static_assert(CA_REC + 1 == CA_BND && CA_REC + 2 <= FBN_CALIB_BIN_WORDS, "bin layout");
+  hipStream_t st = (hipStream_t)stream;
+  if (!out || !status || ((uintptr_t)out & 7)) {
+    fbn_set_error("fbn_calib_reduce: status and an 8-B aligned out are required");
+    return FBN_ERR_ARG;
+  }
+  if (n < 0 || n >= (1ll << 31)) { fbn_set_error("fbn_calib_reduce: need 0 <= n < 2^31"); return FBN_ERR_ARG; }
+  if (bins < 1 || bins > FBN_CALIB_MAX_BINS) { fbn_set_error("fbn_calib_reduce: bins must be in [1, 1024]"); return FBN_ERR_ARG; }
+  const int words = 2 * bins * FBN_CALIB_BIN_WORDS;
+  if (n == 0) {
+    fbn_launch(calib_empty_kernel, dim3((words + 1 + 255) / 256), dim3(256), 0, st, words, (const unsigned*)status, out);
+    FBN_CHECK_LAUNCH();
+    return FBN_OK;
+  }
+  if (!keys || !ws || ((uintptr_t)ws & 15)) {
+    fbn_set_error("fbn_calib_reduce: keys and a 16-B aligned ws are required");
+    return FBN_ERR_ARG;
+  }
+  const CalibLayout L = calib_layout(n);
+  if (ws_bytes < L.total) { fbn_set_error("fbn_calib_reduce: ws smaller than fbn_calib_workspace_size(n)"); return FBN_ERR_ARG; }
+  char* w = (char*)ws;
+  uint64_t* wide = (uint64_t*)(w + L.wide);
+  uint64_t* sorted = (uint64_t*)(w + L.sorted);
+  unsigned long long* bsum = (unsigned long long*)(w + L.bsum);
+  unsigned long long* bnd = (unsigned long long*)(w + L.bnd);
+  const uint32_t un = (uint32_t)n, nb1 = L.nb1;
+  fbn_launch(calib_widen_kernel, dim3(nb1 - 1u), dim3(256), 0, st, keys, un, wide, status);
+  const int rc = fbn_sort_u64(wide, n, 31, w + L.sortws, L.total - L.sortws, sorted, stream);
+  if (rc != FBN_OK) return rc;
+  fbn_launch(calib_sums_kernel, dim3(nb1), dim3(256), 0, st, (const uint64_t*)sorted, un, nb1, bsum);
+  for (int k = 0; k < CA_REC; ++k)
+    fbn_launch(scan_top_kernel<unsigned long long>, dim3(1), dim3(256), 0, st, bsum + (size_t)k * nb1, nb1);
+  fbn_launch(calib_bound_kernel, dim3(2 * (bins + 1)), dim3(256), 0, st, (const uint64_t*)sorted, un, bins, nb1,
+             (const unsigned long long*)bsum, bnd);
+  fbn_launch(calib_table_kernel, dim3((2 * bins + 255) / 256), dim3(256), 0, st, (const uint64_t*)sorted, bins,
+             (const unsigned long long*)bnd, (const unsigned*)status, out);
   FBN_CHECK_LAUNCH();
   return FBN_OK;
 }

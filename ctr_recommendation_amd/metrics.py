@@ -17,10 +17,15 @@ fixed-shape tree (bitwise reproducible for the same sample sequence).
 4 more bytes per sample, and compute() also returns the AUC averaged over the groups that hold both
 classes -- exact integer counts per group, float64 sums in ascending id order, so the numbers do not
 depend on the samples' order, on the update sizes or on the rank split.
+
+``calibration(bins)`` is the other half of validation (§20): the reliability table of the samples held, in
+equal-width and in equal-mass bins, as exact integers from one device sort and one prefix sum, and the
+ECE / MCE / PCOC / Brier score derived from it on the host with Python integers.
 """
 from __future__ import annotations
 
 import math
+from fractions import Fraction
 from typing import Dict, Optional
 
 import numpy as np
@@ -60,6 +65,66 @@ def gauc_from_table(table: Dict) -> Dict:
             "n_groups": int(len(mixed)), "n_groups_mixed": n_groups_mixed, "n_mixed": n_mixed}
 
 
+_FX_ONE = 1 << 32                                # the fixed-point 1.0 of the calibration sums
+_CALIB_COLS = ("n", "n_pos", "sum_p", "sum_p_pos", "sum_p2")
+
+
+def _entropy(n: int, n_pos: int) -> float:
+    """-(r ln r + (1 - r) ln(1 - r)) of the base rate r = n_pos / n; 0 for a single class, NaN for n == 0."""
+    n, n_pos = int(n), int(n_pos)
+    if n == 0:
+        return float("nan")
+    if n_pos == 0 or n_pos == n:
+        return 0.0
+    r, q = n_pos / n, (n - n_pos) / n            # both correctly rounded
+    return -(r * math.log(r) + q * math.log(q))
+
+
+def normalized_entropy(logloss: float, n: int, n_pos: int) -> float:
+    """The log-loss over the entropy of the base rate n_pos / n (below 1: better than predicting the
+    base rate everywhere).  NaN when the entropy is 0 (a single class) or n == 0."""
+    h = _entropy(n, n_pos)
+    return float(logloss) / h if h > 0.0 else float("nan")
+
+
+def calibration_from_table(table: Dict) -> Dict:
+    """The calibration scalars of a reliability table: ``table["width"]`` and ``table["mass"]`` (the
+    equal-width and the equal-mass plane, as ``DeviceMetrics.calibration()`` returns them), each a dict
+    of integer arrays of length B: n, n_pos, sum_p, sum_p_pos, sum_p2 with sum_p = sum of
+    rint(p 2^32) and sum_p2 = sum of rint(p^2 2^32).  Python integers throughout: every result is an
+    exact numerator over an exact denominator, divided once (int / int is correctly rounded).  With
+    S = 2^32:
+      ece      sum_b |n_pos_b S - sum_p_b| / (n S) over the width plane; ece_mass over the mass plane
+      mce      max over the non-empty width bins of |n_pos_b S - sum_p_b| / (n_b S)
+      pcoc     sum_p / (n_pos S): predicted over observed clicks; NaN without a positive
+      brier    (sum_p2 - 2 sum_p_pos + n_pos S) / (n S)
+      entropy  of the base rate n_pos / n; 0 for a single class
+    All NaN when n == 0.  Needs no GPU."""
+    def col(plane, k):
+        v = table[plane][k]
+        v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        return [int(x) for x in v.reshape(-1)]
+    S = _FX_ONE
+    w = {k: col("width", k) for k in _CALIB_COLS}
+    m = {k: col("mass", k) for k in ("n", "n_pos", "sum_p")}
+    B = len(w["n"])
+    n, n_pos = sum(w["n"]), sum(w["n_pos"])
+    out = {"bins": B, "n": n, "n_pos": n_pos}
+    nan = float("nan")
+    if n == 0:
+        out.update(ece=nan, mce=nan, ece_mass=nan, pcoc=nan, brier=nan, entropy=nan)
+        return out
+    gap_w = [abs(a * S - b) for a, b in zip(w["n_pos"], w["sum_p"])]
+    gap_m = [abs(a * S - b) for a, b in zip(m["n_pos"], m["sum_p"])]
+    worst = max(Fraction(g, c * S) for g, c in zip(gap_w, w["n"]) if c)
+    sum_p = sum(w["sum_p"])
+    out.update(ece=sum(gap_w) / (n * S), mce=worst.numerator / worst.denominator, ece_mass=sum(gap_m) / (n * S),
+               pcoc=sum_p / (n_pos * S) if n_pos else nan,
+               brier=(sum(w["sum_p2"]) - 2 * sum(w["sum_p_pos"]) + n_pos * S) / (n * S),
+               entropy=_entropy(n, n_pos))
+    return out
+
+
 class DeviceMetrics:
     """Streaming exact ROC-AUC + log-loss of up to ``capacity`` samples held as keys on ``device``;
     ``grouped``: also their group ids, for the per-group AUC."""
@@ -85,6 +150,8 @@ class DeviceMetrics:
         self._gws: Optional[torch.Tensor] = None
         self._table: Optional[torch.Tensor] = None         # [n][4] int64 of the last grouped reduce
         self._table_rows: Optional[int] = None             # its G; None: stale
+        self._cws: Optional[torch.Tensor] = None           # calibration(): workspace and table
+        self._ctab: Optional[torch.Tensor] = None
 
     def _new_rec(self) -> torch.Tensor:
         return torch.zeros(_REC + (_lib.FBN_GAUC_REC_WORDS if self.grouped else 0), dtype=torch.int64, device=self.device)
@@ -146,6 +213,12 @@ class DeviceMetrics:
             self._table = torch.empty((max(1, n), 4), dtype=torch.int64, device=self.device)
         return self._gws, self._table
 
+    @staticmethod
+    def _check_status(word: int) -> None:
+        status = int(word) & 0xFFFFFFFF
+        if status:
+            raise ValueError("DeviceMetrics: " + "; ".join(msg for bit, msg in _STATUS if status & bit))
+
     def _reduce(self, keys: torch.Tensor, n: int, rec: torch.Tensor, gids: Optional[torch.Tensor] = None) -> Dict:
         ws = self._workspace(n)
         with torch.cuda.device(self.device):
@@ -157,9 +230,7 @@ class DeviceMetrics:
                      table.data_ptr(), rec.data_ptr() + 8 * _REC, rec.data_ptr() + 32, _lib.stream_handle(self.device))
         self._table_rows = None
         host = rec.cpu().numpy()                 # the one device-to-host read: record(s) + status
-        status = int(host[4]) & 0xFFFFFFFF
-        if status:
-            raise ValueError("DeviceMetrics: " + "; ".join(msg for bit, msg in _STATUS if status & bit))
+        self._check_status(int(host[4]))
         u2, n_pos, n_neg = int(host[0]), int(host[1]), int(host[2])
         ll_sum = float(host[3:4].view(np.float64)[0])
         total = n_pos + n_neg
@@ -198,8 +269,14 @@ class DeviceMetrics:
         rank-major order: key order does not enter the AUC or the grouped numbers, and the log-loss
         tree sees the same sequence everywhere, so all ranks return identical numbers.
         stage_on_cpu: gather through host tensors (gloo)."""
+        return self._reduce(*self._gather(group, stage_on_cpu))
+
+    def _gather(self, group, stage_on_cpu: bool):
+        """(keys, n, rec, gids) a reduce runs over: this instance's own, or with a process group every
+        rank's, all-gathered in rank-major order (collective), with a fresh record holding the OR of the
+        ranks' status words.  compute(group=) and calibration(group=) share it."""
         if group is None:
-            return self._reduce(self.keys, self.count, self.rec, self.gids)
+            return self.keys, self.count, self.rec, self.gids
         import torch.distributed as dist
         world = dist.get_world_size(group)
         counts = [None] * world
@@ -231,4 +308,59 @@ class DeviceMetrics:
         for r in range(1, world):
             status |= got[r, width - 1:]
         rec.view(torch.int32)[8:9] = status
-        return self._reduce(keys.contiguous(), total, rec, gids)
+        return keys.contiguous(), total, rec, gids
+
+    @staticmethod
+    def _check_bins(bins) -> int:
+        if isinstance(bins, bool) or int(bins) != bins or not 1 <= int(bins) <= _lib.FBN_CALIB_MAX_BINS:
+            raise ValueError(f"calibration bins must be an integer in [1, {_lib.FBN_CALIB_MAX_BINS}], not {bins!r}")
+        return int(bins)
+
+    def _calibrate(self, keys: torch.Tensor, n: int, rec: torch.Tensor, bins: int) -> Dict:
+        need = int(call("fbn_calib_workspace_size", n))
+        if self._cws is None or self._cws.numel() < need:
+            self._cws = None
+            self._cws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        words = 2 * bins * _lib.FBN_CALIB_BIN_WORDS + 1
+        if self._ctab is None or self._ctab.numel() < words:
+            self._ctab = torch.empty(words, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            call("fbn_calib_reduce", keys.data_ptr(), n, bins, self._cws.data_ptr(), self._cws.numel(),
+                 self._ctab.data_ptr(), rec.data_ptr() + 32, _lib.stream_handle(self.device))
+        host = self._ctab[:words].cpu().numpy()  # the one device-to-host read: both planes + status
+        self._check_status(int(host[-1]))
+        t = host[:-1].reshape(2, bins, _lib.FBN_CALIB_BIN_WORDS)
+        planes = {}
+        for k, name in enumerate(("width", "mass")):
+            plane = {c: t[k, :, w].copy() for w, c in enumerate(_CALIB_COLS)}      # sums below 2^63: int64 holds them
+            ends = t[k, :, 5].copy().view(np.uint32).reshape(bins, 2)              # little-endian: {p_min, p_max} bits
+            empty = plane["n"] == 0
+            for c, e in (("p_lo", 0), ("p_hi", 1)):
+                v = ends[:, e].copy().view(np.float32)
+                v[empty] = np.nan
+                plane[c] = v
+            planes[name] = plane
+        out = calibration_from_table(planes)
+        out.update(planes)
+        return out
+
+    def calibration(self, bins: int = 10, group=None, stage_on_cpu: bool = False) -> Dict:
+        """The reliability table of the samples held (they stay: the call can be repeated with other
+        bins, before or after compute()) and the calibration scalars derived from it (§20):
+        {"bins", "n", "n_pos", "ece", "mce", "ece_mass", "pcoc", "brier", "entropy", "width", "mass"}.
+        "width" (equal-width bins: min(B - 1, floor(p B)) in float64) and "mass" (equal-mass bins: ranks
+        [floor(b n / B), floor((b + 1) n / B)) of the sorted keys, ties split with the negatives first)
+        are dicts of numpy arrays of length B: n, n_pos, sum_p, sum_p_pos, sum_p2 (int64; the sums are of
+        rint(p 2^32) and rint(p^2 2^32)) and p_lo, p_hi (float32; NaN for an empty bin).  Every number
+        is exact and independent of the samples' order, the update sizes and the rank split; the scalars
+        are calibration_from_table()'s.  One sort of the keys, one read.  Raises the ValueError compute()
+        raises for the same status word.  group / stage_on_cpu: as in compute() (the same all-gather)."""
+        bins = self._check_bins(bins)
+        keys, n, rec, _ = self._gather(group, stage_on_cpu)
+        return self._calibrate(keys, n, rec, bins)
+
+    def compute_and_calibrate(self, bins: int, group=None, stage_on_cpu: bool = False):
+        """(compute(), calibration(bins)) over one gather of the keys."""
+        bins = self._check_bins(bins)
+        keys, n, rec, gids = self._gather(group, stage_on_cpu)
+        return self._reduce(keys, n, rec, gids), self._calibrate(keys, n, rec, bins)

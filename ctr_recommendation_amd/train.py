@@ -65,7 +65,9 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
         log=print, overrides: Optional[Dict] = None) -> Dict:
     """Train as src/train_fibinet.py does; returns {"best_auc", "history": [(epoch, loss, auc)],
     "valid_logloss": [per epoch], "trainer"}; with the model-config key ``valid_group_by`` (a batch
-    column, e.g. user_id) also "valid_gauc": [per epoch] and a `` | Valid GAUC: `` field on the epoch line."""
+    column, e.g. user_id) also "valid_gauc": [per epoch] and a `` | Valid GAUC: `` field on the epoch line;
+    with ``valid_calibration_bins`` (B in [1, 1024]) also "valid_ece", "valid_pcoc", "valid_ne": [per epoch]
+    and `` | Valid ECE: ... | PCOC: ... | NE: ... `` on the epoch line."""
     import torch.distributed as dist
 
     from .loader import make_loaders
@@ -100,6 +102,13 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
     best_auc, history, valid_logloss = 0.0, [], []
     group_by = model_cfg.get("valid_group_by")            # e.g. user_id: also report the per-group AUC
     valid_gauc = []
+    calib_bins = model_cfg.get("valid_calibration_bins")  # e.g. 10: also report the calibration of the probabilities
+    valid_ece, valid_pcoc, valid_ne = [], [], []
+    ev_args = {}
+    if group_by:
+        ev_args["group_by"] = str(group_by)
+    if calib_bins:
+        ev_args["calibration_bins"] = int(calib_bins)
     ckpt = checkpoint or os.path.join("..", "checkpoints", "FiBiNET_best.pth")
     for epoch in range(n_epochs):
         t0 = time.perf_counter()
@@ -127,7 +136,7 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
         dt = time.perf_counter() - t0
         # validation (:133-146): eval-mode probabilities of the whole split, packed and counted on the
         # device (metrics.DeviceMetrics: the exact AUC, the double utils.compute_auc returns on them)
-        ev = trainer.evaluate(valid_loader, group_by=str(group_by)) if group_by else trainer.evaluate(valid_loader)
+        ev = trainer.evaluate(valid_loader, **ev_args)
         valid_loader.check(world=world)
         auc = logloss = None
         if len(valid_loader):
@@ -141,6 +150,13 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
             gauc = float(ev["gauc"]) if len(valid_loader) else None
             valid_gauc.append(gauc)
             line += f" | Valid GAUC: {gauc if gauc is None else f'{gauc:.4f}'}"
+        if calib_bins:
+            ece, pcoc, ne = ((float(ev[k]) for k in ("ece", "pcoc", "ne")) if len(valid_loader) else (None,) * 3)
+            valid_ece.append(ece)
+            valid_pcoc.append(pcoc)
+            valid_ne.append(ne)
+            fmt = lambda v: v if v is None else f"{v:.4f}"            # noqa: E731
+            line += f" | Valid ECE: {fmt(ece)} | PCOC: {fmt(pcoc)} | NE: {fmt(ne)}"
         log0(line)
         if auc is not None and auc > best_auc:
             best_auc = auc
@@ -153,6 +169,8 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
     out = {"best_auc": best_auc, "history": history, "valid_logloss": valid_logloss, "trainer": trainer}
     if group_by:
         out["valid_gauc"] = valid_gauc
+    if calib_bins:
+        out.update(valid_ece=valid_ece, valid_pcoc=valid_pcoc, valid_ne=valid_ne)
     return out
 
 

@@ -1222,7 +1222,8 @@ class FiBiNETTrainer:
         return (a["logits"] if logits else a["probs"]).clone()
 
     @torch.no_grad()
-    def evaluate(self, loader_or_batches, metrics=None, group_by: Optional[str] = None) -> Dict:
+    def evaluate(self, loader_or_batches, metrics=None, group_by: Optional[str] = None,
+                 calibration_bins: Optional[int] = None) -> Dict:
         """Validation metrics of (batch, labels) pairs without a per-batch host transfer: predict()'s
         eval-mode forward per batch, its probabilities packed straight into a metrics.DeviceMetrics
         (one launch per batch), then one exact device reduce and one 40-byte read.  Returns
@@ -1233,9 +1234,15 @@ class FiBiNETTrainer:
         hold this rank's samples); default: one sized for the input, kept for the next call.
         group_by: a batch column of integer ids (e.g. "user_id"): the metrics are grouped by it and the
         result also holds {"gauc", "gauc_macro", "gauc_clicks", "n_groups", "n_groups_mixed", "n_mixed"}
-        (metrics.DeviceMetrics(grouped=True)); KeyError if a batch lacks the column."""
-        from .metrics import DeviceMetrics
+        (metrics.DeviceMetrics(grouped=True)); KeyError if a batch lacks the column.
+        calibration_bins: an integer B in [1, 1024]: the result also holds {"ece", "mce", "ece_mass",
+        "pcoc", "brier", "ne"} and "calibration", DeviceMetrics.calibration(B)'s dict (the reliability
+        table in equal-width and equal-mass bins); ne = logloss / entropy of the base rate.  The keys are
+        gathered once for both reduces at N > 1."""
+        from .metrics import DeviceMetrics, normalized_entropy
         grouped = group_by is not None
+        if calibration_bins is not None:
+            calibration_bins = DeviceMetrics._check_bins(calibration_bins)
         if metrics is None:
             ds = getattr(loader_or_batches, "ds", None)
             if ds is not None:                                # DeviceLoader: this rank's share of every batch
@@ -1253,10 +1260,16 @@ class FiBiNETTrainer:
             probs = self.predict(batch)
             if probs.numel():
                 metrics.update(probs, labels, group_ids=ids)
+        group = None
         if self.world > 1:
             group = self.group if self.group is not None else dist.group.WORLD
+        if calibration_bins is None:
             return metrics.compute(group=group, stage_on_cpu=self.stage_on_cpu)
-        return metrics.compute()
+        out, cal = metrics.compute_and_calibrate(calibration_bins, group=group, stage_on_cpu=self.stage_on_cpu)
+        out.update({k: cal[k] for k in ("ece", "mce", "ece_mass", "pcoc", "brier")})
+        out["ne"] = normalized_entropy(out["logloss"], cal["n"], cal["n_pos"])
+        out["calibration"] = cal
+        return out
 
     def check_ids(self) -> None:
         """Raise what the reference would have raised since the last check (one 4-byte read):

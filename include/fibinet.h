@@ -708,6 +708,34 @@ size_t fbn_gauc_workspace_size(long long n);
 int fbn_gauc_reduce(const uint32_t* keys, const uint32_t* gids, long long n, void* ws, size_t ws_bytes,
                     unsigned long long* table, void* out, unsigned* status, void* stream);
 
+/* ---------------------------------------------------------------- device metrics: calibration table
+ * The reference validates ranking only (roc_auc_score / log_loss, src/utils.py:18-32); whether the
+ * probabilities are right -- a reliability table, ECE / MCE, predicted over observed clicks, the Brier
+ * score -- a user has to bin on the host from every batch's probabilities (src/train_fibinet.py:133-146).
+ * This builds the table from the keys fbn_eval_pack wrote, by one device sort and one prefix sum.
+ * With p the fp32 probability of a key (a key above (0x3F800000 << 1) | 1 is counted as 1.0 and sets bit
+ * 3 of *status), y its low bit and B = bins in [1, FBN_CALIB_MAX_BINS]:
+ *   fx(p) = rint((double)p * 2^32), fx2(p) = rint((double)p * (double)p * 2^32): exact float64 products,
+ *   round-half-even, both <= 2^32, so every sum over n < 2^31 samples is an integer below 2^63 and
+ *   independent of any order;
+ *   equal-width bin of p = min(B - 1, (int)floor((double)p * B)) (the product in float64);
+ *   equal-mass bin b = the keys of ranks [floor(b n / B), floor((b + 1) n / B)) in ascending KEY order:
+ *   ties of p are split with the negatives first, whatever the input order; bins may be empty (B > n).
+ * fbn_calib_reduce over keys[0 .. n), 0 <= n < 2^31:
+ *   out [2][B][FBN_CALIB_BIN_WORDS] uint64 (8-B aligned), plane 0 equal width, plane 1 equal mass, per bin
+ *     0 n_b   1 n_pos_b   2 sum fx(p)   3 sum fx(p) over the positives   4 sum fx2(p)
+ *     5 bits(p_min) | bits(p_max) << 32 (0 for an empty bin)   6, 7 zero
+ *   followed by one word out[2 * B * 8]: the value of *status after this reduce (one copy reads both).
+ *   n == 0 writes zeros (and the status word).  keys is not modified.
+ *   ws: >= fbn_calib_workspace_size(n) bytes (host-only query), 16-B aligned.  A null pointer, n < 0 or
+ *   n >= 2^31, bins outside [1, 1024] and a small or misaligned ws return FBN_ERR_ARG before any device
+ *   work.  No atomics on the sums, no host sync, no allocation. */
+#define FBN_CALIB_MAX_BINS 1024
+#define FBN_CALIB_BIN_WORDS 8
+size_t fbn_calib_workspace_size(long long n);
+int fbn_calib_reduce(const uint32_t* keys, long long n, int bins, void* ws, size_t ws_bytes, uint64_t* out,
+                     unsigned* status, void* stream);
+
 /* ---------------------------------------------------------------- serving: catalogue scoring + top-K
  * Replaces the per-row scoring loop of src/Prediction.py:106-113 when the rows are the U x M pairs
  * (user u, catalogue item m): the field construction of src/model_fibinet.py:152-188 is split into

@@ -1,0 +1,181 @@
+"""Host side of the calibration metrics (no GPU): the constants, the workspace query, the argument
+guards that return before any launch, the bin rule, and metrics.calibration_from_table over the
+reference tables against a plain float64 computation."""
+import ctypes
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+from tests import _calib_ref as C
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# derived, not measured: fx and fx2 each round by at most 2^-33 per sample, so a bin's |n_pos - sum p| is
+# off by at most n_b 2^-33 and ece / mce by at most 2^-33; the Brier score by at most (1 + 2 r) 2^-33 <=
+# 2^-32 for a base rate r <= 1/2 (the families' is below 0.2 from n = 63 on); the float64 reference
+# (math.fsum: one rounding per sum) adds a few 2^-53.  Measured on ctr at 70 001, B = 10: 4e-13 at most.
+ATOL = 2.0 ** -32
+SCALARS = ("ece", "mce", "ece_mass", "pcoc", "brier", "entropy")
+
+
+def test_constants_mirror_the_header():
+    from ctr_recommendation_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "fibinet.h")).read()
+    src = open(os.path.join(ROOT, "ctr_recommendation_amd", "csrc", "metrics.hip")).read()
+    for text in (hdr, src):
+        assert int(re.search(r"#define FBN_CALIB_MAX_BINS (\d+)", text).group(1)) == _lib.FBN_CALIB_MAX_BINS == 1024
+        assert int(re.search(r"#define FBN_CALIB_BIN_WORDS (\d+)", text).group(1)) == _lib.FBN_CALIB_BIN_WORDS == 8
+    assert _lib.SIGNATURES["fbn_calib_reduce"][1][2] is _lib.I     # bins
+
+
+def test_workspace_query_is_host_only_granular_and_monotone():
+    from ctr_recommendation_amd import _lib
+    h = _lib.lib()
+    f = h.fbn_calib_workspace_size
+    T = _lib.FBN_SORT_TILE
+    ns = (0, 1, 63, 64, 65, 255, 256, 257, T - 1, T, T + 1, 2 * T + 1, 65537, 70001, 1 << 20, (1 << 31) - 1)
+    sizes = [f(n) for n in ns]
+    assert all(s > 0 and s % 256 == 0 for s in sizes)
+    assert sizes == sorted(sizes) and sizes[0] < sizes[-3] < sizes[-2] < sizes[-1]
+    assert f(-5) == f(0)
+    for n, s in zip(ns, sizes):                                    # the sort's workspace and the widened keys
+        assert s >= h.fbn_sort_u64_workspace_size(n) + 8 * n, n
+
+
+def test_entry_point_refuses_bad_arguments_before_launching():
+    from ctr_recommendation_amd import _lib
+    h = _lib.lib()
+    buf = (ctypes.c_ulonglong * 64)()
+    a = ctypes.addressof(buf)                                      # a host address: the guards never touch it
+    err = lambda: h.fbn_last_error()                               # noqa: E731
+    big = 1 << 40
+    f = h.fbn_calib_reduce
+    assert f(a, 1 << 31, 10, a + 256, big, a, a, None) == 1 and b"fbn_calib_reduce" in err() and b"2^31" in err()
+    assert f(a, -1, 10, a + 256, big, a, a, None) == 1 and b"fbn_calib_reduce" in err()
+    assert f(a, 8, 0, a + 256, big, a, a, None) == 1 and b"fbn_calib_reduce" in err() and b"bins" in err()
+    assert f(a, 8, 1025, a + 256, big, a, a, None) == 1 and b"bins" in err()
+    assert f(a, 8, -3, a + 256, big, a, a, None) == 1 and b"bins" in err()
+    assert f(None, 8, 10, a + 256, big, a, a, None) == 1 and b"fbn_calib_reduce" in err()    # no keys
+    assert f(a, 8, 10, None, big, a, a, None) == 1 and b"fbn_calib_reduce" in err()          # no workspace
+    assert f(a, 8, 10, a + 256, big, None, a, None) == 1 and b"fbn_calib_reduce" in err()    # no table
+    assert f(a, 8, 10, a + 256, big, a, None, None) == 1 and b"fbn_calib_reduce" in err()    # no status word
+    assert f(a, 0, 10, None, 0, None, a, None) == 1                                          # n == 0 still writes
+    assert f(a, 0, 10, None, 0, a, None, None) == 1
+    assert f(a, 8, 10, a + 256, big, a + 4, a, None) == 1                                    # misaligned table
+    assert f(a, 8, 10, a + 260, big, a, a, None) == 1                                        # misaligned workspace
+    assert f(a, 8, 10, a + 256, h.fbn_calib_workspace_size(8) - 1, a, a, None) == 1
+    assert b"fbn_calib_workspace_size" in err()
+    assert f(a, 8, 10, a + 256, 0, a, a, None) == 1
+
+
+def test_device_metrics_calibration_needs_a_hip_device():
+    from ctr_recommendation_amd.metrics import DeviceMetrics
+    assert callable(DeviceMetrics.calibration)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        DeviceMetrics(8, "cpu").calibration(10)
+
+
+def test_the_width_rule_multiplies_in_float64():
+    five_sixths = np.float32(5 / 6)
+    assert int(C.width_bin(five_sixths, 6)) == 4                   # float64(float32(5/6)) * 6 < 5
+    assert int(np.floor(five_sixths * np.float32(6))) == 5         # ... an fp32 product rounds up to 5.0
+    y, p = C.case("sevenths", 4099)
+    t = C.table("sevenths", 4099, 6)
+    sel = p == five_sixths
+    assert sel.sum() > 100
+    assert t["width"]["n"][4] >= int(sel.sum()) and t["width"]["p_hi"][4] == five_sixths
+    assert t["width"]["n"][5] == int((p == 1).sum())               # only p = 1.0 reaches the last bin
+    # hundredths at B = 100: the reference's bins are the float64 rule's, which is not the fp32 product's
+    grid = (np.arange(101) / 100.0).astype(np.float32)
+    rule = np.minimum(99, np.floor(grid.astype(np.float64) * 100).astype(np.int64))
+    fp32 = np.minimum(99, np.floor(grid * np.float32(100)).astype(np.int64))
+    assert int((rule != fp32).sum()) == 48
+    y, p = C.case("hundredths", 70001)
+    t = C.table("hundredths", 70001, 100)
+    assert np.array_equal(t["width"]["n"], np.bincount(C.width_bin(p, 100), minlength=100))
+    assert not np.array_equal(t["width"]["n"],
+                              np.bincount(np.minimum(99, np.floor(p * np.float32(100)).astype(np.int64)), minlength=100))
+
+
+def test_fixed_point_rounds_half_to_even():
+    p = np.array([2.0 ** -33, 3 * 2.0 ** -33, 2.0 ** -149, 1.0, 0.5], dtype=np.float32)
+    y = np.array([1, 1, 0, 1, 0], dtype=np.float32)
+    t = C.ref_table(y, p, 1)["width"]
+    assert int(t["sum_p"][0]) == 0 + 2 + 0 + (1 << 32) + (1 << 31)
+    assert int(t["sum_p_pos"][0]) == 2 + (1 << 32)
+    assert int(t["sum_p2"][0]) == (1 << 32) + (1 << 30)
+    assert t["p_lo"][0] == np.float32(2.0 ** -149) and t["p_hi"][0] == 1.0
+
+
+@pytest.mark.parametrize("bins", (1, 6, 10, 100, 1024))
+@pytest.mark.parametrize("n", (1, 2, 65, 4099, 70001))
+@pytest.mark.parametrize("family", C.FAMILIES)
+def test_calibration_from_table_against_plain_float64(family, n, bins):
+    from ctr_recommendation_amd.metrics import calibration_from_table
+    y, p = C.case(family, n)
+    t = C.table(family, n, bins)
+    out = calibration_from_table(t)
+    ref = C.direct(y, p, bins)
+    assert out["bins"] == bins and out["n"] == n and out["n_pos"] == int(y.sum())
+    for plane in ("width", "mass"):                                # both planes partition the same samples
+        for c in C.COLS:
+            assert int(t[plane][c].sum()) == int(t["width"][c].sum()), (plane, c)
+    for k in SCALARS:
+        print(k, out[k], ref[k])
+        if math.isnan(ref[k]):
+            assert math.isnan(out[k]), k
+        else:
+            assert abs(out[k] - ref[k]) <= ATOL, k
+    assert 0.0 <= out["ece"] <= out["mce"] <= 1.0 and 0.0 <= out["brier"] <= 1.0
+    if bins == 1:                                                  # one bin: both planes are the whole sample
+        assert out["ece"] == out["ece_mass"] == out["mce"]
+        if out["n_pos"]:
+            assert abs(out["ece"] - abs(1.0 - out["pcoc"]) * out["n_pos"] / n) <= ATOL
+
+
+def test_nan_and_single_class_conventions():
+    from ctr_recommendation_amd.metrics import calibration_from_table, normalized_entropy
+    z = {c: np.zeros(4, dtype=np.int64) for c in C.COLS}
+    out = calibration_from_table({"width": z, "mass": z})
+    assert out["bins"] == 4 and out["n"] == 0 and out["n_pos"] == 0
+    assert all(math.isnan(out[k]) for k in SCALARS)
+    p = np.array([0.25, 0.5, 0.75], dtype=np.float32)
+    neg = calibration_from_table(C.ref_table(np.zeros(3, np.float32), p, 2))
+    assert math.isnan(neg["pcoc"]) and neg["entropy"] == 0.0
+    assert neg["ece"] == 0.5 and neg["brier"] == (0.0625 + 0.25 + 0.5625) / 3 and neg["mce"] == 0.625
+    pos = calibration_from_table(C.ref_table(np.ones(3, np.float32), p, 2))
+    assert pos["pcoc"] == 0.5 and pos["entropy"] == 0.0 and pos["brier"] == (0.5625 + 0.25 + 0.0625) / 3
+    both = calibration_from_table(C.ref_table(np.array([0, 1, 1, 0], np.float32), np.full(4, 0.5, np.float32), 3))
+    assert both["entropy"] == math.log(2.0) and both["ece"] == 0.0 and both["pcoc"] == 1.0 and both["brier"] == 0.25
+    assert normalized_entropy(0.5, 4, 2) == 0.5 / math.log(2.0)
+    assert normalized_entropy(0.3, 1000, 170) == 0.3 / calibration_from_table(
+        C.ref_table(np.r_[np.ones(170), np.zeros(830)].astype(np.float32), np.full(1000, 0.17, np.float32), 5))["entropy"]
+    for n, n_pos in ((0, 0), (5, 0), (5, 5)):
+        assert math.isnan(normalized_entropy(0.5, n, n_pos))
+
+
+def test_families_have_the_shapes_the_gpu_tests_rely_on():
+    y, p = C.case("ctr", 70001)
+    t = C.table("ctr", 70001, 10)
+    from ctr_recommendation_amd.metrics import calibration_from_table
+    out = calibration_from_table(t)
+    assert t["width"]["n"][0] > 0.98 * 70001                       # the pile-up: equal-width bins see one bin
+    assert 0.7 < out["pcoc"] < 0.82                                # visibly under-predicting
+    assert int(t["mass"]["n"].min()) == 7000 and int(t["mass"]["n"].max()) == 7001
+    y, p = C.case("all_equal", 4099)                               # one tie across every mass boundary: negatives first
+    t = C.table("all_equal", 4099, 10)
+    n_neg = 4099 - int(y.sum())
+    first_pos = int(np.searchsorted(np.cumsum(t["mass"]["n"]), n_neg, side="right"))
+    assert all(t["mass"]["n_pos"][:first_pos] == 0) and all(t["mass"]["n_pos"][first_pos + 1:] == t["mass"]["n"][first_pos + 1:])
+    y, p = C.case("edges", 4099)
+    assert (p == 0).sum() > 100 and np.signbit(p).any() and (p == 1).any() and (p == np.float32(2.0 ** -149)).any()
+    t = C.table("edges", 4099, 16)                                 # k/16 opens bin k; its lower neighbour closes bin k - 1
+    for k in range(1, 16):
+        assert t["width"]["p_lo"][k] == np.float32(k / 16)
+        assert t["width"]["p_hi"][k - 1] == np.nextafter(np.float32(k / 16), np.float32(0))
+    t = C.table("uniform", 63, 1024)                               # B > n: empty bins in both planes
+    assert (t["mass"]["n"] == 0).sum() == 1024 - 63 and (t["width"]["n"] == 0).sum() > 900
+    assert np.isnan(t["mass"]["p_lo"][t["mass"]["n"] == 0]).all()
