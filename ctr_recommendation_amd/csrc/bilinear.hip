@@ -24,6 +24,7 @@
 // lane overwrites exactly the elements it alone read) and becomes the second MFMA's B operand;
 // that MFMA (A = W rows, K = n) accumulates straight onto the elementwise part of dV.
 #include "common.h"
+#include "fields_common.h"   // the fields backward's body and folds (the fused backward below)
 #include <algorithm>
 
 namespace {
@@ -238,6 +239,146 @@ __global__ void __launch_bounds__(nthreads<D>(), 2) bilinear_bwd_kernel(const vo
   }
 }
 
+// ------------------------------------------------------------------------------ bilinear + fields backward
+// One launch for bilinear_bwd_kernel<128, true> and fields_bwd_kernel<128, 0, 3> (fields.hip): dV never
+// leaves the chip.  The dependency is per sample, so a workgroup runs the bilinear backward of 16
+// samples (phase A), hands their dV over in LDS, and runs the fields backward of the same samples
+// (phase B).  Sample ownership is the fields backward's -- its partial row partials[block] sums its
+// samples in a fixed order, so which samples a lane group takes decides the low bits: with nblk
+// blocks, wave gw = 4 blk + w takes samples (gw + it 4 nblk) 2 + grp, it = 0, 1.  Tile slot
+// s = 8 it + 2 w + grp holds that sample (two runs of 8 consecutive samples); a column of the
+// transposed MFMA depends on its own sample only, so U, dU and dV are the bits of the 16-consecutive
+// tiling.  Every result is bit-identical to the two launches.
+constexpr int FB_PITCH = 5 * 128 + 4;   // floats per sample of the dV tile: +4 spreads a store group's 8 samples over the banks
+constexpr int FB_RMAX = 3;              // SENET width the fused form is built for (the reference's)
+
+__device__ __forceinline__ int fb_sample(int blk, int nblk, int s) { return 8 * blk + (s & 7) + (s >> 3) * 8 * nblk; }
+
+template <bool SLOT>
+__global__ void __launch_bounds__(256, 2) bilinear_fields_bwd_kernel(const short* __restrict__ dc, int ldc,
+                                                                    const short* __restrict__ V16,
+                                                                    const short* __restrict__ WT16,
+                                                                    const short* __restrict__ W16,
+                                                                    short* __restrict__ dU16, FieldBwdArgs p) {
+  FBN_MAIN_PRIO();
+  constexpr int D = 128, NT = 256, RB = 2, G = D / 4, SPW = 64 / G, CH = D / 8;
+  // phase A: the V / dU tile and the weight image (as bilinear_bwd_kernel); phase B, over them: the dV
+  // tile [16][FB_PITCH] f32, then the fields backward's 4 wave slices and SENET staging
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  short* sV = reinterpret_cast<short*>(smem);
+  short* sW = sV + 5 * TS * D;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int blk = blockIdx.x, nblk = gridDim.x, B = p.B;
+  {
+    constexpr int N = TS * 5 * CH / NT;     // the V tile: LDS row f*16 + s <- V16[sample(s)][f]
+    bf16x8 v[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const int i = tid + j * NT, m = i / CH, b = fb_sample(blk, nblk, m / 5);
+      v[j] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+      if (b < B) v[j] = *reinterpret_cast<const bf16x8*>(V16 + ((size_t)b * 5 + m % 5) * D + (i % CH) * 8);
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const int i = tid + j * NT, m = i / CH;
+      *reinterpret_cast<bf16x8*>(sV + swz<D>((m % 5) * TS + m / 5, (i % CH) * 8)) = v[j];
+    }
+  }
+  stage_w<D, NT>(sW, WT16, tid);
+  __syncthreads();
+  WStage<D, NT> wnext;
+  wnext.load(W16, tid);                     // the W image for dV += dU W^T: in flight meanwhile
+  f32x4 acc[RB][5];
+#pragma unroll
+  for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+    for (int f = 0; f < 5; ++f) acc[rb][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  mfma_5<D>(acc, sW, sV, w, lane);          // acc = U^T (recomputed: never stored)
+  __syncthreads();                          // no wave still reads the V tile: dU may overwrite it
+  const int s = lane & 15, lq = lane >> 4;
+  const int bs = fb_sample(blk, nblk, s);
+  const bool live = bs < B;
+  const short* dcr = dc + (size_t)(live ? bs : 0) * ldc;
+#pragma unroll
+  for (int rb = 0; rb < RB; ++rb) {
+    const int n0 = 32 * w + 16 * rb + 4 * lq;
+    f32x4 v[5], gv[5], gu[5];
+#pragma unroll
+    for (int f = 0; f < 5; ++f) {
+      v[f] = ld_bf4(sV + swz<D>(f * TS + s, n0));
+      gv[f] = live ? ld_bf4(dcr + f * D + n0) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      gu[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      const f32x4 gp = live ? ld_bf4(dcr + (5 + k) * D + n0) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      gv[PI[k]] += gp * acc[rb][PJ[k]];
+      gu[PJ[k]] += gp * v[PI[k]];
+    }
+#pragma unroll
+    for (int f = 0; f < 5; ++f) {
+      const bf16x4 t = to_bf4(gu[f]);
+      *reinterpret_cast<bf16x4*>(sV + swz<D>(f * TS + s, n0)) = t;
+      if (live) *reinterpret_cast<bf16x4*>(dU16 + ((size_t)bs * 5 + f) * D + n0) = t;
+    }
+#pragma unroll
+    for (int f = 0; f < 5; ++f) acc[rb][f] = gv[f];
+  }
+  __syncthreads();                          // every wave is done with the W^T image and the dU tile is whole
+  wnext.store(sW, tid);
+  // phase B's reads of its first sample (all but dV): in flight under the second MFMA and the hand-over
+  const int q = lane % G, grp = lane / G;
+  const int b_0 = (4 * blk + w) * SPW + grp, b_1 = b_0 + 4 * nblk * SPW;
+  FieldsBwdIn in = fields_bwd_load<D>(p, b_0 < B ? b_0 : 0, q);
+  float* gvec = p.gvec;
+  if constexpr (SLOT) {   // the ring slot of this step, chosen on the device (as fields_bwd_kernel)
+    gvec += (size_t)(__builtin_amdgcn_readfirstlane(*p.slot_step) % p.ring_n) * p.ring_stride;
+    if (blk == 0 && tid == 0) *p.slot_cell = gvec;
+  }
+  __syncthreads();
+  mfma_5<D>(acc, sW, sV, w, lane);          // acc = dV^T = elementwise part + W dU^T
+  __syncthreads();                          // every wave has read the dU tile and the W image: the dV tile overlays them
+  float* tile = smem;
+  float* sp = smem + TS * FB_PITCH;         // 4 wave slices of P floats + SENET staging
+  const int P = 13 * p.R + 6 + 3 * D + p.n_cate * D;
+#pragma unroll
+  for (int rb = 0; rb < RB; ++rb) {
+    const int k0 = 32 * w + 16 * rb + 4 * lq;
+#pragma unroll
+    for (int f = 0; f < 5; ++f) *reinterpret_cast<f32x4*>(tile + s * FB_PITCH + f * D + k0) = acc[rb][f];
+  }
+  for (int i = tid; i < 4 * P; i += NT) sp[i] = 0.f;
+  __syncthreads();
+
+  // phase B: fields_bwd_kernel<128, 0, 3>'s loop over this wave's samples, dv from the tile
+  float* sv = sp + 4 * P + (w * SPW + grp) * (12 + 2 * FB_RMAX);
+  float* w_ct = sp + w * P + 13 * p.R + 6 + 2 * D;
+  FieldsBwdAcc<D, FB_RMAX> facc;
+  facc.zero();
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int b = it ? b_1 : b_0;
+    if (b - grp >= B) break;                // wave-uniform, as the loop bound of fields_bwd_kernel
+    const bool blive = b < B;
+    FieldsBwdIn nxt;
+    if (it == 0) nxt = fields_bwd_load<D>(p, b_1 < B ? b_1 : 0, q);   // the second sample's reads under the first's arithmetic
+    f32x4 dx0 = {0.f, 0.f, 0.f, 0.f}, dx1 = {0.f, 0.f, 0.f, 0.f};
+    long long lk = -1, vw = -1;
+    if (blive) {
+      const float* dvs = tile + (8 * it + SPW * w + grp) * FB_PITCH + 4 * q;
+      f32x4 dv[5];
+#pragma unroll
+      for (int f = 0; f < 5; ++f) dv[f] = *reinterpret_cast<const f32x4*>(dvs + f * D);
+      lk = in.lk;
+      vw = in.vw;
+      fields_bwd_sample<D, 0, FB_RMAX>(p, gvec, b, lane, in, dv, sv, facc, dx0, dx1);
+    }
+    fields_bwd_cate<D>(w_ct, p.n_cate, lane, blive, lk, vw, dx0, dx1);
+    if (it == 0) in = nxt;
+  }
+  fields_bwd_fold<D, FB_RMAX>(p, sp, facc);
+}
+
 }  // namespace
 
 extern "C" int fbn_bilinear_supported(int D) { return D == 16 || D == 32 || D == 64 || D == 128; }
@@ -287,4 +428,65 @@ extern "C" int fbn_bilinear_bwd(const void* dc, int ldc, int dc_bf16, const shor
 #undef FBN_BILINEAR_BWD
   FBN_CHECK_LAUNCH();
   return FBN_OK;
+}
+
+// LDS of the fused backward: phase A's images, or phase B's dV tile + fields slices + staging
+static size_t bilinear_fields_lds(int R, int n_cate) {
+  const size_t a = (size_t)(5 * TS * 128 + 128 * 128) * sizeof(short);
+  const size_t b = (size_t)TS * FB_PITCH * sizeof(float) + fields_bwd_lds(128, R, n_cate, FB_RMAX);
+  return std::max(a, b);
+}
+
+extern "C" int fbn_bilinear_fields_bwd_supported(int B, int D, int R, int n_cate) {
+  if (D != 128 || B <= 0 || R < 1 || R > FB_RMAX || n_cate < 0) return 0;
+  // a fields-backward block must own at most 16 samples (one MFMA tile): two iterations per wave
+  if ((long long)B > 16LL * fields_grid(B, D, FBN_FB_MAXBLK)) return 0;
+  return bilinear_fields_lds(R, n_cate) <= 80 * 1024;   // two workgroups per CU
+}
+
+extern "C" int fbn_bilinear_fields_bwd(const void* dc, int ldc, const short* V16, const short* WT16, const short* W16,
+                                       short* dU16, const int64_t* likes, const int64_t* views, const float* hmm,
+                                       const float* ln_g, const float* ln_b, float ln_eps, const float* w1,
+                                       const float* b1, const float* w2, int R, int n_cate, const float* cate,
+                                       const float* X, const float* a, const float* cnt, float* dhmm, short* dhmm16,
+                                       float* partials, float* const* param_grads, float* gvec, const int* slot_step,
+                                       void* slot_cell, int ring_n, long long ring_stride, double* gnorm, int B, int D,
+                                       void* stream) {
+  if (B <= 0) return FBN_OK;
+  if (!fbn_bilinear_fields_bwd_supported(B, D, R, n_cate)) {
+    fbn_set_error("fbn_bilinear_fields_bwd: needs D = 128, R <= 3, at most 16 samples per fields-backward block and "
+                  "80 KB of LDS (fbn_bilinear_fields_bwd_supported)");
+    return FBN_ERR_UNSUPPORTED;
+  }
+  if (!dc || !V16 || !WT16 || !W16 || !dU16 || (ldc & 3) || ((uintptr_t)dc & 7) || ((uintptr_t)V16 & 15) ||
+      ((uintptr_t)WT16 & 15) || ((uintptr_t)W16 & 15) || ((uintptr_t)dU16 & 7)) {
+    fbn_set_error("fbn_bilinear_fields_bwd: bf16 dc, V, W^T, W, dU16 required and aligned (16 B; dc, dU16 8 B), ldc % 4 == 0");
+    return FBN_ERR_ARG;
+  }
+  if (!likes || !views || !hmm || !ln_g || !ln_b || !w1 || !b1 || !w2 || !cate || !X || !a || !cnt || !partials ||
+      !gvec || ((uintptr_t)gvec & 15)) {
+    fbn_set_error("fbn_bilinear_fields_bwd: the fields operands, partials and gvec (16-B aligned) are required");
+    return FBN_ERR_ARG;
+  }
+  if (slot_step && (!slot_cell || ring_n < 1 || ring_stride < (long long)B * 2 * D || (ring_stride & 3))) {
+    fbn_set_error("fbn_bilinear_fields_bwd: slot form: cell; ring_n >= 1, ring_stride >= B*2*D, % 4 == 0");
+    return FBN_ERR_ARG;
+  }
+  FieldBwdArgs p = {};
+  p.likes = likes; p.views = views; p.hmm = hmm; p.ln_g = ln_g; p.ln_b = ln_b; p.w1 = w1; p.b1 = b1; p.w2 = w2;
+  p.cate = cate; p.X = X; p.a = a; p.cnt = cnt; p.dhmm = dhmm; p.dhmm16 = dhmm16; p.partials = partials;
+  p.gvec = gvec; p.gnorm = gnorm;
+  p.slot_step = slot_step; p.slot_cell = (float**)slot_cell; p.ring_n = ring_n; p.ring_stride = ring_stride;
+  p.B = B; p.R = R; p.n_cate = n_cate; p.ln_eps = ln_eps;
+  const dim3 grid((unsigned)fields_grid(B, D, FBN_FB_MAXBLK));
+  const unsigned lds = (unsigned)bilinear_fields_lds(R, n_cate);
+  hipStream_t st = (hipStream_t)stream;
+  const short* dc16 = (const short*)dc;
+  if (slot_step)
+    fbn_launch(bilinear_fields_bwd_kernel<true>, grid, dim3(256), lds, st, dc16, ldc, V16, WT16, W16, dU16, p);
+  else
+    fbn_launch(bilinear_fields_bwd_kernel<false>, grid, dim3(256), lds, st, dc16, ldc, V16, WT16, W16, dU16, p);
+  FBN_CHECK_LAUNCH();
+  if (!param_grads) return FBN_OK;   // deferred: the caller sums the partial rows
+  return fbn_fields_reduce_partials(partials, param_grads, B, D, R, n_cate, st);
 }

@@ -43,6 +43,9 @@ _SPLIT_BWD = os.environ.get("FBN_SPLIT_BWD", "0") == "1"
 _SPLIT3 = os.environ.get("FBN_SPLIT3", "1") != "0"
 # bf16, one process: the BN1 backward first pass inside the epilogue of its dgrad GEMM (A/B knob)
 _BN1_BWD_IN_GEMM = os.environ.get("FBN_BN1_BWD_IN_GEMM", "1") == "1"
+# bf16, one process, d = 128: the fields backward inside the fused bilinear backward's launch, dV in
+# LDS (fbn_bilinear_fields_bwd; bit-identical to the two launches; A/B knob)
+_FIELDS_IN_BILINEAR = os.environ.get("FBN_FIELDS_IN_BILINEAR", "1") == "1"
 
 
 def wa_remap(d: int):
@@ -972,10 +975,19 @@ def backward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], a: Dict
         gemm(dh1pre, p["mlp.0.weight"], dc, B, KC, H1, H1, 21 * d, KC, False, False, rB=wa_remap(d), bf16=sb,
              stream=st)
     # bilinear backward
-    dV = tmp("dV", (B, 5, d))
+    R = cfg.R
+    ncate = p["cate_emb.weight"].shape[0]
+    # ... with the fields backward in its launch (dV never stored) when nothing has to run between them
+    fields_in_bil = bool(_FIELDS_IN_BILINEAR and a.get("fused_bilinear") and pos is None
+                         and not (hooks and "after_bilinear_bwd" in hooks)
+                         and (gvec is not None or gslot is not None)
+                         and _lib.lib().fbn_bilinear_fields_bwd_supported(B, d, R, ncate))
+    dV = None if fields_in_bil else tmp("dV", (B, 5, d))
     v16 = bf and not cfg.bilinear_each
     dU16 = tmp("dU16", (B, 5, d), torch.bfloat16) if v16 else None
-    if a.get("fused_bilinear"):
+    if fields_in_bil:
+        pass                                        # dU16 comes from the fused launch below
+    elif a.get("fused_bilinear"):
         # one launch: dU and dV = dc_V + pair terms + dU W^T (U recomputed on the MFMA)
         call("fbn_bilinear_bwd", ptr(dc), KC, int(dc.dtype == torch.bfloat16), ptr(a["Vc16"]), ptr(w16["WT"]),
              ptr(w16["W"]), ptr(dV), ptr(dU16), B, d, st)
@@ -1021,12 +1033,10 @@ def backward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], a: Dict
     if hooks and "after_bilinear_bwd" in hooks:   # trainer: the weight gradients so far launched early
         hooks["after_bilinear_bwd"](sums)
     # fields backward: SENET, LN, cate + item-table scatter
-    R = cfg.R
-    ncate = p["cate_emb.weight"].shape[0]
     P = _lib.lib().fbn_fields_bwd_partials_size(d, R, ncate)
     nblk = _lib.lib().fbn_fields_bwd_grid(B, d)
     partials = tmp("partials", (nblk, P))
-    dhmm = tmp("dhmm", (B, d))
+    dhmm = None if fields_in_bil else tmp("dhmm", (B, d))   # bf16, one process: only dhmm16 is read
     dhmm16 = tmp("dhmm16", (B, d), torch.bfloat16) if bf else None
     dhs = img("dhmm", B, d) if s3 else None
     seq = batch.get("item_seq", None)
@@ -1045,7 +1055,15 @@ def backward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], a: Dict
         _lib.keep(outs_arr)
         outs = ctypes.cast(outs_arr, ctypes.c_void_p).value
     evb = _probe_start(probe, "fields_bwd")     # bench / tools: the fields backward
-    if gslot is not None:
+    if fields_in_bil:
+        ring, ring_n, ring_stride, step, cell = gslot if gslot is not None else (gvec, 0, 0, None, None)
+        call("fbn_bilinear_fields_bwd", ptr(dc), KC, ptr(a["Vc16"]), ptr(w16["WT"]), ptr(w16["W"]), ptr(dU16),
+             ptr(batch["likes_level"]), ptr(batch["views_level"]), ptr(a["hmm"]), ptr(p["mm_proj.1.weight"]),
+             ptr(p["mm_proj.1.bias"]), LN_EPS, ptr(p["senet.excitation.0.weight"]),
+             ptr(p["senet.excitation.0.bias"]), ptr(p["senet.excitation.2.weight"]), R, ncate,
+             ptr(p["cate_emb.weight"]), ptr(a["X"]), ptr(a["a"]), ptr(a["cnt"]), None, ptr(dhmm16), ptr(partials),
+             outs, ptr(ring), ptr(step), ptr(cell), ring_n, ring_stride, ptr(gnorm), B, d, st)
+    elif gslot is not None:
         ring, ring_n, ring_stride, step, cell = gslot
         call("fbn_fields_bwd_slot", ptr(batch["item_id"]), ptr(seq) if Lr else None, ptr(batch["likes_level"]),
              ptr(batch["views_level"]), ptr(a["hmm"]), ptr(p["mm_proj.1.weight"]), ptr(p["mm_proj.1.bias"]), LN_EPS,
@@ -1066,6 +1084,9 @@ def backward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], a: Dict
     _probe_end(evb)
     if hooks and "after_fields_bwd" in hooks:     # N > 1: the gradient rows are complete -> exchange
         hooks["after_fields_bwd"]()
+    if fields_in_bil:                             # the bilinear.W gradient, its dU16 operand now written
+        if not sums.gemm_slabs(a["Vc16"], dU16, g["bilinear.W"], d, d, 5 * B, d, d, d, True, False, stream=st):
+            wg.run(lambda s: gemm(a["Vc16"], dU16, g["bilinear.W"], d, d, 5 * B, d, d, d, True, False, stream=s))
     if bf:
         if not sums.gemm_slabs(dhmm16, w16["x"], g["mm_proj.0.weight"], d, 128, B, d, 128, 128, True, False,
                                stream=st):

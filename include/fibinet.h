@@ -625,6 +625,26 @@ int fbn_bilinear_supported(int D);
 int fbn_bilinear_fwd(const short* V16, const short* WT16, short* c, int B, int D, int ldc, void* stream);
 int fbn_bilinear_bwd(const void* dc, int ldc, int dc_bf16, const short* V16, const short* WT16, const short* W16,
                      float* dV, short* dU16, int B, int D, void* stream);
+/* fbn_bilinear_bwd (bf16 dc) and the fields backward that reads its dV, in ONE launch: dV stays in
+ * LDS.  Each workgroup runs the bilinear backward of the 16 samples one fields-backward block owns,
+ * then their fields backward (fbn_fields_bwd's MODE 0 with per-sample vectors): dU16, dhmm16, dhmm,
+ * the vectors, gnorm and every row of partials are bit-identical to fbn_bilinear_bwd followed by
+ * fbn_fields_bwd / fbn_fields_bwd_slot.  Arguments as theirs, without dV and without the ids of the
+ * dense table gradient; dhmm may be NULL (not written: bf16 mode reads dhmm16 only).  gvec: the
+ * vectors [B][2][D], or with slot_step the ring base of fbn_fields_bwd_slot (slot_cell, ring_n,
+ * ring_stride as there; all null / 0 for the gvec form).
+ * fbn_bilinear_fields_bwd_supported: 1 when D = 128, R <= 3, a fields-backward block owns at most 16
+ * samples (B <= 16 fbn_fields_bwd_grid(B, D)) and the LDS of (R, n_cate) leaves two workgroups per
+ * CU (<= 80 KB); else the entry point returns FBN_ERR_UNSUPPORTED without launching and the caller
+ * makes the two launches. */
+int fbn_bilinear_fields_bwd_supported(int B, int D, int R, int n_cate);
+int fbn_bilinear_fields_bwd(const void* dc, int ldc, const short* V16, const short* WT16, const short* W16,
+                            short* dU16, const int64_t* likes, const int64_t* views, const float* hmm,
+                            const float* ln_g, const float* ln_b, float ln_eps, const float* w1, const float* b1,
+                            const float* w2, int R, int n_cate, const float* cate, const float* X, const float* a,
+                            const float* cnt, float* dhmm, short* dhmm16, float* partials,
+                            float* const* param_grads, float* gvec, const int* slot_step, void* slot_cell, int ring_n,
+                            long long ring_stride, double* gnorm, int B, int D, void* stream);
 
 /* ---------------------------------------------------------------- device collator
  * Replaces BatchCollator.__call__ (src/dataloader.py:69-121) and InferenceCollator.__call__
