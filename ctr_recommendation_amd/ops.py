@@ -612,7 +612,7 @@ def forward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], cfg: Fwd
             hc = a["hot_cnt"] = _lib.persistent(lambda: torch.zeros(V, dtype=torch.int32, device=dev))
             a["hot_list"] = _lib.persistent(lambda: torch.zeros(256, dtype=torch.int32, device=dev))
             a["hot_n"] = _lib.persistent(lambda: torch.zeros(1, dtype=torch.int32, device=dev))
-        H = 8192 // d
+        H = min(256, 8192 // d)     # the list holds 256 ids, and the kernel stages min(8192 / d, 256) rows
         call("fbn_hot_rows", ptr(item_id), ptr(seq) if Lr else None, B, Lr, V, ptr(hc), ptr(a["hot_list"]),
              ptr(a["hot_n"]), H, _GATHER_HOT, 0, st)
         call("fbn_fields_fwd_hot", ptr(item_id), ptr(seq) if Lr else None, ptr(batch["likes_level"]),
