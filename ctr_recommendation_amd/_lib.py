@@ -149,6 +149,7 @@ SIGNATURES = {
     "fbn_eval_reduce": (I, [P, LL, P, SZ, P, P, P]),
     "fbn_sort_u64_workspace_size": (SZ, [LL]),
     "fbn_sort_u64": (I, [P, LL, I, P, SZ, P, P]),
+    "fbn_digest_u64": (I, [P, LL, ctypes.c_ulonglong, P, P]),
     "fbn_eval_pack_groups": (I, [P, LL, P, P, P]),
     "fbn_gauc_workspace_size": (SZ, [LL]),
     "fbn_gauc_reduce": (I, [P, P, LL, P, SZ, P, P, P, P]),

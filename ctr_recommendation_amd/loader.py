@@ -171,6 +171,35 @@ class DeviceLoader:
         self.gen.manual_seed(seed)
         self.missing = torch.zeros(1, dtype=torch.int32, device=self.device)   # train: sticky KeyError flag
         self.epoch = 0
+        self._epoch_gen = None      # the generator's state before the current epoch's permutation was drawn
+        self._in_epoch = False      # an iterator of the current epoch has not run out yet
+        self._skip = 0              # batches the next __iter__ leaves out (load_state_dict)
+
+    def state_dict(self) -> Dict:
+        """The shuffle position: {"epoch", "gen_state"} such that, once loaded, the next ``__iter__``
+        draws the permutation of the epoch being iterated now (the generator as it was BEFORE that
+        epoch's randperm) -- or, between epochs, of the next one.  How far into the epoch the consumer
+        got is the caller's knowledge (a loop that runs one batch ahead has drawn more batches than
+        it has used): pass it to load_state_dict as ``skip``.  Unshuffled loaders carry only "epoch"."""
+        mid = self._in_epoch is not False
+        sd = {"epoch": self.epoch - 1 if mid else self.epoch}
+        if self.shuffle:
+            gs = self._epoch_gen if mid else self.gen.get_state()
+            sd["gen_state"] = gs.clone()
+        return sd
+
+    def load_state_dict(self, sd: Dict, skip: int = 0) -> None:
+        """Resume at state_dict()'s position: the next ``__iter__`` redraws that epoch's permutation and
+        starts at batch `skip`."""
+        if skip < 0 or skip > len(self):
+            raise ValueError(f"skip must be in [0, {len(self)}], not {skip}")
+        if self.shuffle:
+            if "gen_state" not in sd:
+                raise ValueError("loader state of an unshuffled loader loaded into a shuffled one")
+            self.gen.set_state(sd["gen_state"].cpu())
+        self.epoch = int(sd["epoch"])
+        self._in_epoch = False
+        self._skip = int(skip)
 
     def __len__(self) -> int:
         n = len(self.ds)
@@ -212,11 +241,22 @@ class DeviceLoader:
         return out, lab
 
     def __iter__(self) -> Iterator:
+        if self.shuffle:
+            self._epoch_gen = self.gen.get_state()
         perm = self._perm()
         self.epoch += 1
+        first, self._skip = self._skip, 0
+        me = self._in_epoch = object()      # (an abandoned iterator finalised later must not clear its successor's)
+        try:
+            yield from self._batches(perm, first)
+        finally:
+            if self._in_epoch is me:
+                self._in_epoch = False
+
+    def _batches(self, perm: torch.Tensor, first: int) -> Iterator:
         n = len(self.ds)
         B = self.batch_size
-        for i in range(len(self)):
+        for i in range(first, len(self)):
             lo, hi = i * B, min(n, (i + 1) * B)
             # this rank's contiguous share of the global batch (the last, short batch splits too)
             share = -(-(hi - lo) // self.world)

@@ -21,6 +21,13 @@ Same surface and loop as the reference script:
   AUC equal to utils.compute_auc's double), and the best-AUC checkpoint (App. B keys, no
   ``module.`` prefix: :148-152).
 
+What the reference lacks and this launcher adds (opt-in; without these arguments nothing changes and
+nothing extra is written): full-state checkpoints (checkpoint.py: weights, Adam moments, schedule
+position, dropout stream, loader position, the epoch's running loss) every ``--save-every`` optimizer
+steps and at each epoch's end under ``--state-dir``, ``--max-steps K`` (stop cleanly after K steps of
+this invocation, saving first: preemptible jobs), and ``--resume DIR``: the run continues mid-epoch
+and every later loss, metric and bit of state equals the uninterrupted run's.
+
 What differs is underneath: batches come from the HBM-resident loader (loader.py: one collate
 launch per batch, no worker processes, no pageable copies); the loss is accumulated on the device
 and read at the print points (the reference syncs every step with ``loss.item()``); at N > 1
@@ -32,6 +39,7 @@ from __future__ import annotations
 
 import argparse
 import os
+import struct
 import time
 from typing import Dict, Optional, Tuple
 
@@ -61,15 +69,33 @@ def set_seed(seed: int) -> None:
     torch.manual_seed(seed)
 
 
+def _f64_bits(x: float) -> int:
+    return struct.unpack("<q", struct.pack("<d", float(x)))[0]
+
+
+def _f64_from_bits(b: int) -> float:
+    return struct.unpack("<d", struct.pack("<q", int(b)))[0]
+
+
 def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoint: Optional[str] = None,
-        log=print, overrides: Optional[Dict] = None) -> Dict:
+        log=print, overrides: Optional[Dict] = None, resume: Optional[str] = None,
+        save_every: Optional[int] = None, state_dir: Optional[str] = None,
+        max_steps: Optional[int] = None) -> Dict:
     """Train as src/train_fibinet.py does; returns {"best_auc", "history": [(epoch, loss, auc)],
     "valid_logloss": [per epoch], "trainer"}; with the model-config key ``valid_group_by`` (a batch
     column, e.g. user_id) also "valid_gauc": [per epoch] and a `` | Valid GAUC: `` field on the epoch line;
     with ``valid_calibration_bins`` (B in [1, 1024]) also "valid_ece", "valid_pcoc", "valid_ne": [per epoch]
-    and `` | Valid ECE: ... | PCOC: ... | NE: ... `` on the epoch line."""
+    and `` | Valid ECE: ... | PCOC: ... | NE: ... `` on the epoch line.
+
+    Full-state checkpoints (checkpoint.py; also the model-config keys ``resume_from``,
+    ``checkpoint_every_steps``, ``state_dir``): save_every: one every that many optimizer steps and at
+    each epoch's end, under state_dir (default: the resume directory, else ../checkpoints/state);
+    max_steps: stop after that many steps of THIS call, saving first (the result then has
+    "stopped": True); resume: continue the run saved under that directory, mid-epoch, one batch ahead
+    as before -- its losses, metrics and state equal the uninterrupted run's bit for bit."""
     import torch.distributed as dist
 
+    from . import checkpoint as state_ckpt
     from .loader import make_loaders
     from .model_fibinet import build_model
     from .trainer import FiBiNETTrainer
@@ -110,10 +136,43 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
     if calib_bins:
         ev_args["calibration_bins"] = int(calib_bins)
     ckpt = checkpoint or os.path.join("..", "checkpoints", "FiBiNET_best.pth")
-    for epoch in range(n_epochs):
+    resume = resume if resume is not None else model_cfg.get("resume_from")
+    save_every = int(save_every if save_every is not None else model_cfg.get("checkpoint_every_steps") or 0)
+    state_dir = state_dir if state_dir is not None else model_cfg.get("state_dir")
+    saving = bool(state_dir) or save_every > 0 or max_steps is not None
+    if saving and not state_dir:
+        state_dir = resume or os.path.join("..", "checkpoints", "state")
+    lists = {"valid_logloss": valid_logloss, "valid_gauc": valid_gauc, "valid_ece": valid_ece,
+             "valid_pcoc": valid_pcoc, "valid_ne": valid_ne}
+
+    def save_state(epoch: int, steps: int, loss_sum: float) -> None:
+        """The run as it stands: `steps` steps of (0-based) `epoch` done, their losses summing to loss_sum."""
+        state_ckpt.save(state_dir, trainer, extra={
+            "epoch": epoch, "steps": steps, "loss_sum_bits": _f64_bits(loss_sum), "best_auc": best_auc,
+            "history": [list(h) for h in history], "lists": {k: list(v) for k, v in lists.items()},
+            "loader": train_loader.state_dict()})
+
+    start_epoch = start_steps = 0
+    start_sum = 0.0
+    if resume:
+        extra = state_ckpt.load(resume, trainer)
+        start_epoch, start_steps = int(extra["epoch"]), int(extra["steps"])
+        start_sum = _f64_from_bits(extra["loss_sum_bits"])
+        best_auc = float(extra["best_auc"])
+        history += [tuple(h) for h in extra["history"]]
+        for k, v in lists.items():
+            v += list(extra["lists"][k])
+        train_loader.load_state_dict(extra["loader"], skip=start_steps)
+        log0(f"Resumed from {resume} | Epoch {start_epoch + 1} | Step {start_steps} | "
+             f"LR: {trainer.current_lr():.6f}")
+    done_here, stopped = 0, False
+    for epoch in range(start_epoch, n_epochs):
         t0 = time.perf_counter()
         total = torch.zeros((), dtype=torch.float64, device=device)
         steps = 0
+        if epoch == start_epoch and start_steps:
+            total.fill_(start_sum)
+            steps = start_steps
         # one batch ahead: step() gets the following batch too, whose ids are routed (N > 1) and
         # whose table rows are caught up (lazy table Adam) during the current step
         it = iter(train_loader)
@@ -130,6 +189,18 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
                 # the print's sync anyway: an item_id without item_info raises here, within 200
                 # steps of the batch (the reference raises at that batch, src/dataloader.py:104-106)
                 train_loader.check(world=world)
+            done_here += 1
+            stopped = max_steps is not None and done_here >= max_steps
+            # mid-epoch state (the epoch's last step is saved after its validation, below)
+            if saving and cur is not None and (stopped or (save_every and trainer.host_step % save_every == 0)):
+                trainer.check_ids()
+                train_loader.check(world=world)
+                save_state(epoch, steps, float(total.item()))
+            if stopped:
+                break
+        if stopped and cur is not None:
+            log0(f"Stopped after {done_here} steps at Epoch {epoch + 1} | Step {steps}; state saved under {state_dir}")
+            break
         trainer.check_ids()
         train_loader.check(world=world)
         avg_loss = float(total.item()) / steps if steps else 0.0
@@ -165,8 +236,16 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
                 os.makedirs(os.path.dirname(os.path.abspath(ckpt)), exist_ok=True)
                 torch.save(sd, ckpt)
                 log0(f"New best FiBiNET AUC; saved to {ckpt}")
-    log0(f"Done. Best AUC: {best_auc:.4f}")
+        if saving:
+            save_state(epoch + 1, 0, 0.0)
+        if stopped:
+            log0(f"Stopped after {done_here} steps at the end of Epoch {epoch + 1}; state saved under {state_dir}")
+            break
+    if not stopped:
+        log0(f"Done. Best AUC: {best_auc:.4f}")
     out = {"best_auc": best_auc, "history": history, "valid_logloss": valid_logloss, "trainer": trainer}
+    if stopped:
+        out["stopped"] = True
     if group_by:
         out["valid_gauc"] = valid_gauc
     if calib_bins:
@@ -179,8 +258,13 @@ def main(argv=None):
     ap.add_argument("--config")
     ap.add_argument("--epochs", type=int)
     ap.add_argument("--checkpoint")
+    ap.add_argument("--resume", metavar="DIR", help="continue the run whose full state was saved under DIR")
+    ap.add_argument("--save-every", type=int, metavar="S", help="save the full training state every S optimizer steps")
+    ap.add_argument("--state-dir", metavar="DIR", help="where the full-state checkpoints go")
+    ap.add_argument("--max-steps", type=int, metavar="K", help="save the state and stop after K steps of this invocation")
     args = ap.parse_args(argv)
-    out = run(args.config, epochs=args.epochs, checkpoint=args.checkpoint)
+    out = run(args.config, epochs=args.epochs, checkpoint=args.checkpoint, resume=args.resume,
+              save_every=args.save_every, state_dir=args.state_dir, max_steps=args.max_steps)
     out["trainer"].close()
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         import torch.distributed as dist

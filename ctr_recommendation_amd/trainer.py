@@ -1399,3 +1399,104 @@ class FiBiNETTrainer:
         self.last.copy_(self.step_dev.expand_as(self.last))     # loaded rows are current (device step)
         if self.pend is not None:
             self.pend.fill_(-1)
+
+    # ------------------------------------------------------------------ full training state (resume)
+    # what load_training_state() compares with the trainer it loads into (all but table_adam, whose
+    # "lazy" and "eager" are bit-identical and may differ between save and load)
+    _STATE_CHECKED = ("d", "V", "L", "world", "rank", "rows_lo", "rows_local", "total_steps", "lr", "wd", "optimizer",
+                      "beta2", "eps", "max_norm", "compute_dtype", "bilinear_type", "R", "sync_bn")
+
+    def _state_meta(self) -> Dict:
+        c = self.fcfg
+        return {"host_step": int(self.host_step), "d": int(self.d), "V": int(self.V), "L": int(self.L),
+                "rows_lo": int(self.rows_lo), "rows_local": int(self.rows_local), "world": int(self.world),
+                "rank": int(self.rank), "total_steps": int(self.total_steps), "lr": float(self.lr),
+                "wd": float(self.wd), "optimizer": self.optimizer, "table_adam": self.table_adam,
+                "beta2": float(self.beta2), "eps": float(self.eps), "max_norm": float(self.max_norm),
+                "compute_dtype": "bf16" if c.bf16 else ("bf16_fwd" if c.fwd16 else "fp32"),
+                "bilinear_type": "each" if c.bilinear_each else "all", "R": int(c.R),
+                "deterministic": bool(self.deterministic), "sync_bn": bool(self.sync_bn)}
+
+    def _state_tensors(self) -> Dict[str, torch.Tensor]:
+        """name -> device tensor of everything a later step reads once the lazy table Adam is flushed."""
+        out = {"E": self.E, "Em": self.Em, "Ev": self.Ev, "flat_p": self.flat_p, "flat_m": self.flat_m,
+               "flat_v": self.flat_v}
+        for n in FROZEN + BUFFERS:
+            out[n] = self.p[n]
+        out["step_dev"] = self.step_dev
+        out["rng"] = self.rng
+        return out
+
+    def state_digests(self) -> Dict[str, int]:
+        """checkpoint.digest() of every tensor of the training state as it is on the device now (flush()
+        first to compare a lazy trainer's table with another's)."""
+        from .checkpoint import digest
+        return {n: digest(t) for n, t in self._state_tensors().items()}
+
+    def training_state(self) -> Dict:
+        """Everything needed to continue this run bit for bit in another process: this rank's block of
+        the table and its Adam moments, the flat dense parameters and moments, the frozen table, the
+        BatchNorm buffers, the device step counter (the schedule position) and the dropout stream, as
+        CPU tensors, plus ``meta`` (plain ints / floats / strings) and ``digests`` (name -> digest of
+        the device tensor at save time) -- a dict torch.load(..., weights_only=True) reads back.
+
+        The lazy table Adam is flushed first: every row then has last == step and no pending gradient,
+        so the deferred-gradient ring, the clip-coefficient history, the pre-claims and the row claims
+        carry nothing and are not saved.  The flush is what lazy == eager already guarantees to be
+        invisible: a run that calls this between two steps continues bit-identically.  No collective
+        (every rank saves what it holds)."""
+        self.flush()
+        dev = self._state_tensors()
+        digests = self.state_digests()
+        state = {n: t.detach().cpu() for n, t in dev.items()}       # (.cpu() of a device tensor is a fresh copy)
+        state["meta"] = self._state_meta()
+        state["digests"] = digests
+        return state
+
+    @torch.no_grad()
+    def load_training_state(self, state: Dict) -> None:
+        """Continue the run training_state() saved.  ``meta`` must match this trainer (ValueError naming
+        the field; the batch size may differ, and "lazy" / "eager" table Adam are interchangeable); the
+        tensors are copied INTO the existing buffers (recorded step programs and captured graphs keep
+        their addresses); the row state is reset to "every row current, nothing pending, nothing
+        claimed"; then every tensor's digest is recomputed on the device and compared with the saved one
+        (RuntimeError naming the tensor -- the trainer must not be stepped after it)."""
+        from .checkpoint import digest
+        meta, mine = state["meta"], self._state_meta()
+        for k in self._STATE_CHECKED:
+            if k not in meta or meta[k] != mine[k]:
+                hint = " (a checkpoint resumes at the world size it was saved at: resharding is not supported)" \
+                    if k in ("world", "rank", "rows_lo", "rows_local") else ""
+                raise ValueError(f"training state does not fit this trainer: {k} is {meta.get(k)!r} in the state, "
+                                 f"{mine[k]!r} here{hint}")
+        if (meta.get("table_adam") == "sparse") != (self.table_adam == "sparse"):
+            raise ValueError(f"training state does not fit this trainer: table_adam is {meta.get('table_adam')!r} in "
+                             f"the state, {self.table_adam!r} here (only 'lazy' and 'eager' are interchangeable)")
+        dev = self._state_tensors()
+        for n, t in dev.items():
+            if n not in state:
+                raise ValueError(f"training state lacks {n!r}")
+            src = state[n]
+            if tuple(src.shape) != tuple(t.shape) or src.dtype != t.dtype:
+                raise ValueError(f"training state does not fit this trainer: {n} is {tuple(src.shape)} {src.dtype} "
+                                 f"in the state, {tuple(t.shape)} {t.dtype} here")
+        torch.cuda.synchronize(self.device)        # nothing of an earlier step still reads the buffers
+        for n, t in dev.items():
+            t.copy_(state[n])
+        # row state: every row has had `step` Adam steps, no pending gradient, no pre-claim tag; no claims
+        self.row_state[:, 0:2].zero_()
+        self.row_state[:, 2].copy_(self.step_dev.expand(self.row_state.shape[0]))
+        self.row_state[:, 3].fill_(-1)
+        self.map.fill_(-1)
+        self.slot_row.fill_(-1)
+        self._pre_key = None
+        self._used_pre = False
+        self._bn_synced_at = -1
+        self.host_step = int(meta["host_step"])
+        for n, t in dev.items():
+            want = state["digests"].get(n)
+            got = digest(t)
+            if want is None or int(want) != got:
+                raise RuntimeError(f"training state corrupt: digest of {n} is {got:016x} on the device after the "
+                                   f"upload, {'missing' if want is None else format(int(want), '016x')} in the state; "
+                                   "do not step this trainer")

@@ -701,6 +701,22 @@ int fbn_eval_reduce(const uint32_t* keys, long long n, void* ws, size_t ws_bytes
 size_t fbn_sort_u64_workspace_size(long long n);
 int fbn_sort_u64(const uint64_t* in, long long n, int bits, void* ws, size_t ws_bytes, uint64_t* out, void* stream);
 
+/* ---------------------------------------------------------------- state digest (full-state checkpoints)
+ * The reference saves weights only and checks nothing (src/train_fibinet.py:148-152).  fbn_digest_u64:
+ * an order-independent 64-bit digest of a device buffer, computed where the buffer lives.  x is n_words
+ * 32-bit words w_i, 4-byte aligned (a view into a larger buffer may start anywhere).  The call ADDS to
+ * *out (8-B aligned, the caller zeroes it), mod 2^64,
+ *   sum over i in [0, n_words) of mix64((base + i + 1) * 0x9E3779B97F4A7C15 + w_i)
+ * in unsigned 64-bit arithmetic, mix64 the splitmix64 finaliser
+ *   x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31.
+ * The word's position is part of its key, so permuted words change the digest; the sum is integer, so
+ * the value does not depend on the grid or the order, and chunks compose:
+ *   digest(x[0 .. k)) + digest(x[k .. n), base = k) == digest(x[0 .. n)).
+ * n_words == 0 launches nothing.  n_words < 0, or a NULL / misaligned x or out with n_words > 0, return
+ * FBN_ERR_ARG before any device call.  One launch, no host synchronisation, no allocation. */
+int fbn_digest_u64(const void* x, long long n_words, unsigned long long base, unsigned long long* out,
+                   void* stream);
+
 /* ---------------------------------------------------------------- device metrics: grouped AUC (GAUC)
  * The reference has no per-user metric: this replaces the host-side grouping a user writes around its
  * validation loop (every batch's probabilities, labels and user ids copied to the host as in
