@@ -90,8 +90,11 @@ __device__ __forceinline__ float adam_elem(float& p, float& m, float& v, float g
 // sqrt.  Every table kernel (eager pass, lazy replay, touched / deferred commit, flush) uses this one
 // function, so the lazy replay stays bit-identical to eager dense Adam; the deviation from the IEEE
 // step is bounded by fbn_adam_selftest (a few ulp of the update, far inside the parity tolerance).
-// The dense parameters use the same step (adam_dense_body): adam_elem, the IEEE form in torch's
-// operation order, remains as the self-test's reference.
+// The dense parameters use the same step (adam_dense_body).  What anchors it to torch is
+// tests/test_gpu_adam.py: every kernel that calls it, one launch at a time, against a float64
+// torch-semantics step under bounds derived from the roundings above (tests/_adam_ref.py).
+// adam_elem, the same update unfused in torch's operation order, is only fbn_adam_selftest's
+// comparison arm: no production kernel calls it.
 // rbc2s = 1/sqrt(bc2) from the host schedule table (column 4, computed in double).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 

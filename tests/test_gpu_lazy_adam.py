@@ -4,7 +4,8 @@ The eager twin.  A table [NROWS][D] with m, v and the 16-byte row-state record p
 eagerly for s = 0 .. T: fbn_adam_table(mode = 1) gives every row the zero-gradient step, except the rows
 that carry a deferred gradient at step s, which take fbn_adam_touched in the owner layout (Lp1 = 1:
 gvec [NE][D] = ring slot s % ring_n, slot_row[e] = row, map[row] = e) with that step's clip coefficient
-coef_hist[s].  Those kernels are pinned to torch by other tests and are the definition of "eager".
+coef_hist[s].  Those two kernels are the definition of "eager"; tests/test_gpu_adam.py pins them (and the flush
+of a deferred gradient) to float64 torch Adam, launch by launch, so bit-identity with them carries that anchor.
 
 The lazy copy.  Row r has a replay start k0[r] drawn from [max(0, T - lag_max), T]; it takes the twin's
 (p, m, v) of that row as they stood before step k0[r] (copied across as the twin's loop passes
@@ -36,7 +37,7 @@ FBN_ERR_ARG, FBN_ERR_UNSUPPORTED = 1, 3
 BETA2, EPS, WD = 0.999, 1e-8, 1e-2
 F_WIN = 7             # the rolling window's F
 
-D_ALL = [16, 64, 128, 256]
+D_ALL = [16, 32, 64, 128, 256]
 D_WIDE = [128, 256]
 # (D, decoupled, kind): kind "small" = T 40, lag <= 33, ring of 34 steps; "large" = T 300 = total_steps,
 # lag <= 299, no deferred gradients (past the 256-step LDS window, the table's last row read);
