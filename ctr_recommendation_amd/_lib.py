@@ -155,6 +155,9 @@ SIGNATURES = {
     "fbn_gauc_reduce": (I, [P, P, LL, P, SZ, P, P, P, P]),
     "fbn_calib_workspace_size": (SZ, [LL]),
     "fbn_calib_reduce": (I, [P, LL, I, P, SZ, P, P, P]),
+    "fbn_auc_place_workspace_size": (SZ, [LL]),
+    "fbn_auc_place": (I, [P, LL, P, SZ, P, P, P]),
+    "fbn_delong_reduce": (I, [P, P, P, P, LL, P, P, P]),
     "fbn_rec_item_cache": (I, [P, P, P, P, P, P, F, I, LL, P, P, I, I, P]),
     "fbn_rec_hist_pool": (I, [P, P, LL, P, P, I, I, I, P]),
     "fbn_rec_fields": (I, [P, P, P, P, P, P, I, P, LL, P, P, P, P, I, P, P, P, I, I, P, P, I, I, I, I, P]),
@@ -197,6 +200,7 @@ FBN_SORT_TILE = 2048          # include/fibinet.h: keys per workgroup of fbn_sor
 FBN_GAUC_REC_WORDS = 8        # include/fibinet.h: 8-byte words of fbn_gauc_reduce's record
 FBN_CALIB_MAX_BINS = 1024     # include/fibinet.h: bins of fbn_calib_reduce at most
 FBN_CALIB_BIN_WORDS = 8       # include/fibinet.h: 8-byte words per bin of its table
+FBN_DELONG_REC_WORDS = 8      # include/fibinet.h: 8-byte words of fbn_delong_reduce's record
 
 _lib: Optional[ctypes.CDLL] = None
 

@@ -32,6 +32,7 @@
 // The per-group AUC (GAUC) over an arbitrary 32-bit group id is the second half of this file: it
 // sorts (csrc/sort.hip) where the ungrouped reduce counts.  The calibration table (reliability bins,
 // the sums behind ECE / PCOC / Brier) is the third part: one sort of the keys and one prefix sum.
+// The DeLong placements and their sums (the variance of an AUC, the covariance of two) are the fourth.
 #include "common.h"
 #include "scan.h"                                // ev_block_excl_scan, scan_top_kernel, fbn_sort_u64
 #include <algorithm>
@@ -857,6 +858,203 @@ extern "C" int fbn_calib_reduce(const uint32_t* keys, long long n, int bins, voi
              (const unsigned long long*)bsum, bnd);
   fbn_launch(calib_table_kernel, dim3((2 * bins + 255) / 256), dim3(256), 0, st, (const uint64_t*)sorted, bins,
              (const unsigned long long*)bnd, (const unsigned*)status, out);
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}
+
+// ================================================================ DeLong placements and sums
+// The variance of the AUC and the covariance of two AUCs over the same samples (DeLong et al. 1988), as
+// exact integers.  The placement of a sample is what it adds to U2: for a positive 2 * #negatives with a
+// smaller score + #negatives with an equal score, for a negative 2 * #positives with a larger score +
+// #positives with an equal score.  fbn_auc_place sorts (key, index) pairs -- the index rides in the high
+// word of the u64, above the 32 bits the sort compares -- so that every search runs along the sorted array
+// (neighbouring lanes look for neighbouring scores) and the only uncoalesced access is one 4-byte store
+// per sample:
+//   c  place_compose_kernel   (index << 32) | key (a key above bits(1.0) clamped and flagged, as above)
+//      fbn_sort_u64(bits = 32)
+//   s  place_scan_*           one two-level scan of the negative flags: N[0 .. n]
+//   p  place_kernel           per sorted position the ends [lower, upper) of its tie by binary search; the
+//                             tie's negatives come first, so mid = lower + N[upper] - N[lower]; a positive
+//                             gets 2 N[lower] + (mid - lower), a negative 2 ((n - upper) - (N[n] - N[upper]))
+//                             + (upper - mid), stored at place_out[index]
+// fbn_delong_reduce sums two placement arrays and their products per class: a product is below 2^64 and a
+// sum of n < 2^31 of them below 2^95, so the low and the high 32 bits of each product go to two separate
+// u64 sums (each below 2^63, no carries).  Integer atomics, one per workgroup and word: order-independent.
+#define EV_BAD_PAIR 0x20000u                     // status bit 17: the two key sets' labels differ
+#define FBN_DELONG_REC_WORDS 8                   // include/fibinet.h publishes the same value
+#define DL_BLOCKS_MAX 1024
+
+struct PlaceLayout {
+  size_t comp, sorted, negs, bsum, sortws, total;
+};
+static inline PlaceLayout place_layout(long long n) {
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t un = (size_t)n, nb = (un + 255) / 256;
+  PlaceLayout L;
+  L.comp = 0;
+  L.sorted = L.comp + al(un * 8);
+  L.negs = L.sorted + al(un * 8);
+  L.bsum = L.negs + al((un + 1) * 4);
+  L.sortws = L.bsum + al(nb * 4);
+  L.total = L.sortws + al(fbn_sort_u64_workspace_size(n));
+  return L;
+}
+
+__global__ void __launch_bounds__(256) place_compose_kernel(const uint32_t* __restrict__ keys, uint32_t n,
+                                                            uint64_t* __restrict__ comp, unsigned* status) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  uint32_t key = keys[i];
+  if ((key >> 1) > EV_MAX_BITS) {                // a key fbn_eval_pack did not write: counted as 1.0
+    key = (EV_MAX_BITS << 1) | (key & 1u);
+    atomicOr(status, EV_BAD_KEY);
+  }
+  comp[i] = ((uint64_t)i << 32) | (uint64_t)key;
+}
+
+__global__ void __launch_bounds__(256) place_scan_sums_kernel(const uint64_t* __restrict__ S, uint32_t n,
+                                                              uint32_t* __restrict__ bsum) {
+  __shared__ uint32_t sh[4];
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  uint32_t total;
+  ev_block_excl_scan<4>(i < n ? ((uint32_t)S[i] & 1u) ^ 1u : 0u, sh, total);
+  if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(256) place_scan_apply_kernel(const uint64_t* __restrict__ S, uint32_t n,
+                                                               const uint32_t* __restrict__ bsum, uint32_t* __restrict__ negs) {
+  __shared__ uint32_t sh[4];
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const uint32_t v = i < n ? ((uint32_t)S[i] & 1u) ^ 1u : 0u;
+  uint32_t total;
+  const uint32_t ex = bsum[blockIdx.x] + ev_block_excl_scan<4>(v, sh, total);
+  if (i >= n) return;
+  negs[i] = ex;
+  if (i == n - 1u) negs[n] = ex + v;
+}
+
+__global__ void __launch_bounds__(256) place_kernel(const uint64_t* __restrict__ S, uint32_t n, const uint32_t* __restrict__ negs,
+                                                    uint32_t* __restrict__ place_out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t s = S[i];
+  const uint32_t key = (uint32_t)s, idx = (uint32_t)(s >> 32), score = key >> 1;
+  uint32_t lo = 0u, hi = i;                      // first position of the tie: S[i] itself qualifies
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (((uint32_t)S[mid] >> 1) < score) lo = mid + 1u; else hi = mid;
+  }
+  const uint32_t lower = lo;
+  lo = i + 1u; hi = n;                           // first position past the tie
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (((uint32_t)S[mid] >> 1) <= score) lo = mid + 1u; else hi = mid;
+  }
+  const uint32_t upper = lo;
+  const uint32_t nl = negs[lower], nu = negs[upper], tie_neg = nu - nl;          // the tie's negatives come first
+  uint32_t v;
+  if (key & 1u) v = 2u * nl + tie_neg;                                           // <= 2 n_neg < 2^32
+  else v = 2u * ((n - upper) - (negs[n] - nu)) + ((upper - lower) - tie_neg);    // <= 2 n_pos
+  if (idx < n) place_out[idx] = v;               // always true: the indices are a permutation of [0, n)
+}
+
+// out[0 .. 8) += this workgroup's sums; the launch's record was zeroed before it
+__global__ void __launch_bounds__(256) delong_reduce_kernel(const uint32_t* __restrict__ keys_a, const uint32_t* __restrict__ place_a,
+                                                            const uint32_t* __restrict__ keys_b, const uint32_t* __restrict__ place_b,
+                                                            uint32_t n, unsigned long long* out, unsigned* status) {
+  __shared__ unsigned long long red[4][FBN_DELONG_REC_WORDS];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  unsigned long long acc[FBN_DELONG_REC_WORDS];
+#pragma unroll
+  for (int k = 0; k < FBN_DELONG_REC_WORDS; ++k) acc[k] = 0ull;
+  unsigned bad = 0u;
+  const uint32_t stride = gridDim.x * 256u;      // at most 2^18: i + stride wraps only past n < 2^31
+  for (uint32_t i = blockIdx.x * 256u + tid; i < n; i += stride) {
+    const uint32_t ya = keys_a[i] & 1u;
+    if ((keys_b[i] & 1u) != ya) bad = EV_BAD_PAIR;
+    const unsigned long long pa = place_a[i], pb = place_b[i], prod = pa * pb;
+    if (ya) {
+      acc[0] += 1ull; acc[2] += pa; acc[3] += pb;
+      acc[4] += prod & 0xFFFFFFFFull; acc[5] += prod >> 32;
+    } else {
+      acc[1] += 1ull;
+      acc[6] += prod & 0xFFFFFFFFull; acc[7] += prod >> 32;
+    }
+  }
+  if (bad) atomicOr(status, bad);
+#pragma unroll
+  for (int k = 0; k < FBN_DELONG_REC_WORDS; ++k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
+    if (lane == 0) red[w][k] = acc[k];
+  }
+  __syncthreads();
+  if (tid < FBN_DELONG_REC_WORDS) {
+    const unsigned long long t = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+    if (t) atomicAdd(&out[tid], t);
+  }
+}
+
+__global__ void delong_status_kernel(unsigned long long* out, const unsigned* __restrict__ status) {
+  out[FBN_DELONG_REC_WORDS] = (unsigned long long)*status;
+}
+
+extern "C" size_t fbn_auc_place_workspace_size(long long n) {
+  if (n < 0) n = 0;
+  return place_layout(n).total;
+}
+
+extern "C" int fbn_auc_place(const uint32_t* keys, long long n, void* ws, size_t ws_bytes, uint32_t* place_out,
+                             unsigned* status, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (n < 0 || n >= (1ll << 31)) { fbn_set_error("fbn_auc_place: need 0 <= n < 2^31"); return FBN_ERR_ARG; }
+  if (n == 0) return FBN_OK;
+  if (!keys || !ws || !place_out || !status || ((uintptr_t)ws & 15) || ((uintptr_t)place_out & 3)) {
+    fbn_set_error("fbn_auc_place: keys, status, a 4-B aligned place_out and a 16-B aligned ws are required");
+    return FBN_ERR_ARG;
+  }
+  const PlaceLayout L = place_layout(n);
+  if (ws_bytes < L.total) { fbn_set_error("fbn_auc_place: ws smaller than fbn_auc_place_workspace_size(n)"); return FBN_ERR_ARG; }
+  char* w = (char*)ws;
+  uint64_t* comp = (uint64_t*)(w + L.comp);
+  uint64_t* sorted = (uint64_t*)(w + L.sorted);
+  uint32_t* negs = (uint32_t*)(w + L.negs);
+  uint32_t* bsum = (uint32_t*)(w + L.bsum);
+  const uint32_t un = (uint32_t)n, nb = (un + 255u) / 256u;
+  fbn_launch(place_compose_kernel, dim3(nb), dim3(256), 0, st, keys, un, comp, status);
+  // 32 bits = four whole digits: the sort never looks at the index above them, it only carries it
+  const int rc = fbn_sort_u64(comp, n, 32, w + L.sortws, L.total - L.sortws, sorted, stream);
+  if (rc != FBN_OK) return rc;
+  fbn_launch(place_scan_sums_kernel, dim3(nb), dim3(256), 0, st, (const uint64_t*)sorted, un, bsum);
+  fbn_launch(scan_top_kernel<uint32_t>, dim3(1), dim3(256), 0, st, bsum, nb);
+  fbn_launch(place_scan_apply_kernel, dim3(nb), dim3(256), 0, st, (const uint64_t*)sorted, un, (const uint32_t*)bsum, negs);
+  fbn_launch(place_kernel, dim3(nb), dim3(256), 0, st, (const uint64_t*)sorted, un, (const uint32_t*)negs, place_out);
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}
+
+extern "C" int fbn_delong_reduce(const uint32_t* keys_a, const uint32_t* place_a, const uint32_t* keys_b,
+                                 const uint32_t* place_b, long long n, unsigned long long* out, unsigned* status,
+                                 void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!out || !status || ((uintptr_t)out & 7)) {
+    fbn_set_error("fbn_delong_reduce: status and an 8-B aligned out are required");
+    return FBN_ERR_ARG;
+  }
+  if (n < 0 || n >= (1ll << 31)) { fbn_set_error("fbn_delong_reduce: need 0 <= n < 2^31"); return FBN_ERR_ARG; }
+  if (n > 0 && (!keys_a || !place_a || !keys_b || !place_b)) {
+    fbn_set_error("fbn_delong_reduce: keys_a, place_a, keys_b and place_b are required");
+    return FBN_ERR_ARG;
+  }
+  if (hipMemsetAsync(out, 0, (size_t)FBN_DELONG_REC_WORDS * 8, st) != hipSuccess) {
+    fbn_set_error("fbn_delong_reduce: memset failed");
+    return FBN_ERR_LAUNCH;
+  }
+  if (n > 0) {
+    const int blocks = (int)std::min<long long>(DL_BLOCKS_MAX, (n + 255) / 256);
+    fbn_launch(delong_reduce_kernel, dim3(blocks), dim3(256), 0, st, keys_a, place_a, keys_b, place_b, (uint32_t)n, out, status);
+  }
+  fbn_launch(delong_status_kernel, dim3(1), dim3(1), 0, st, out, (const unsigned*)status);
   FBN_CHECK_LAUNCH();
   return FBN_OK;
 }

@@ -25,6 +25,7 @@ ECE / MCE / PCOC / Brier score derived from it on the host with Python integers.
 from __future__ import annotations
 
 import math
+import statistics
 from fractions import Fraction
 from typing import Dict, Optional
 
@@ -125,6 +126,85 @@ def calibration_from_table(table: Dict) -> Dict:
     return out
 
 
+_PAIR_STATUS = 1 << 17                           # fbn_delong_reduce: the two key sets' labels differ
+_DELONG_SINGLE = ("auc_var", "auc_se", "ci_lo", "ci_hi")
+_DELONG_PAIR = ("cov", "delta_var", "delta_se", "z", "p_value")
+
+
+def _check_level(level) -> float:
+    if isinstance(level, (bool, str)) or not isinstance(level, (int, float)) or not 0.0 < float(level) < 1.0:
+        raise ValueError(f"level must be a number in (0, 1), not {level!r}")
+    return float(level)
+
+
+def _delong_ints(rec):
+    v = rec.detach().cpu().numpy() if isinstance(rec, torch.Tensor) else rec
+    w = [int(x) for x in np.asarray(v, dtype=object).reshape(-1)[:_lib.FBN_DELONG_REC_WORDS]]
+    if len(w) != _lib.FBN_DELONG_REC_WORDS or min(w) < 0:
+        raise ValueError(f"a DeLong record is {_lib.FBN_DELONG_REC_WORDS} non-negative integers")
+    m, n, ua, ub = w[:4]
+    return m, n, ua, ub, w[4] + (w[5] << 32), w[6] + (w[7] << 32)
+
+
+def _delong_cov(m: int, n: int, ua: int, ub: int, c10: int, c01: int) -> Fraction:
+    """[(m C10 - Ua Ub)(n - 1) + (n C01 - Ua Ub)(m - 1)] / [4 m^2 n^2 (m - 1)(n - 1)], exact; m, n >= 2."""
+    return Fraction((m * c10 - ua * ub) * (n - 1) + (n * c01 - ua * ub) * (m - 1),
+                    4 * m * m * n * n * (m - 1) * (n - 1))
+
+
+def _ratio(f: Fraction) -> float:
+    return f.numerator / f.denominator           # int / int: correctly rounded, at any size
+
+
+def delong_from_record(rec_aa, rec_bb=None, rec_ab=None, level: float = 0.95) -> Dict:
+    """DeLong's variance of an AUC, and the paired test of two AUCs over the same samples, from the
+    integer records of fbn_delong_reduce (``DeviceMetrics.auc_ci()["record"]``): 8 integers
+    {n_pos, n_neg, sum_pos place_a, sum_pos place_b, low / high 32-bit part sums of sum_pos place_a place_b,
+    the same over the negatives}.  Python integers throughout, one division per number; needs no GPU.
+
+    One record (a set against itself): {"auc", "auc_var", "auc_se", "ci_lo", "ci_hi", "level", "n",
+    "n_pos"}; the interval is auc -+ z se clipped to [0, 1], z the normal quantile of (1 + level) / 2.
+    Three records (A against A, B against B, A against B): the above for A, plus {"auc_a", "auc_b",
+    "delta" = auc_a - auc_b, "cov", "delta_var" = var_A + var_B - 2 cov, "delta_se", "z", "p_value"}
+    (two-sided: erfc(|z| / sqrt 2)); delta_var == 0 gives z NaN and p_value 1.0.
+    With fewer than 2 positives or 2 negatives every variance, se, bound, z and p is NaN; auc keeps
+    compute()'s rule (0.5 for an empty class)."""
+    level = _check_level(level)
+    if (rec_bb is None) != (rec_ab is None):
+        raise ValueError("delong_from_record takes one record, or three (A-A, B-B, A-B)")
+    m, n, ua, ua2, c10, c01 = _delong_ints(rec_aa)
+    if ua != ua2:
+        raise ValueError("rec_aa is not the record of a set against itself")
+    nan = float("nan")
+    ok = m >= 2 and n >= 2
+    auc = 0.5 if m == 0 or n == 0 else ua / (2 * m * n)
+    out = {"auc": auc, "level": level, "n": m + n, "n_pos": m}
+    out.update({k: nan for k in _DELONG_SINGLE})
+    if ok:
+        var_a = _delong_cov(m, n, ua, ua, c10, c01)
+        zq = statistics.NormalDist().inv_cdf((1.0 + level) / 2.0)
+        se = math.sqrt(_ratio(var_a))
+        out.update(auc_var=_ratio(var_a), auc_se=se, ci_lo=max(0.0, auc - zq * se), ci_hi=min(1.0, auc + zq * se))
+    if rec_bb is None:
+        return out
+    mb, nb, ub, ub2, d10, d01 = _delong_ints(rec_bb)
+    mx, nx, xa, xb, e10, e01 = _delong_ints(rec_ab)
+    if ub != ub2 or (mb, nb) != (m, n) or (mx, nx) != (m, n) or (xa, xb) != (ua, ub):
+        raise ValueError("the three records do not describe the same samples (class counts or U2 differ)")
+    out["auc_a"] = auc
+    out["auc_b"] = 0.5 if m == 0 or n == 0 else ub / (2 * m * n)
+    out["delta"] = 0.0 if m == 0 or n == 0 else (ua - ub) / (2 * m * n)
+    out.update({k: nan for k in _DELONG_PAIR})
+    if ok:
+        cov = _delong_cov(m, n, ua, ub, e10, e01)
+        dvar = var_a + _delong_cov(m, n, ub, ub, d10, d01) - 2 * cov       # one Fraction, divided once
+        out.update(cov=_ratio(cov), delta_var=_ratio(dvar), delta_se=math.sqrt(_ratio(dvar)), p_value=1.0)
+        if dvar > 0:
+            z = out["delta"] / out["delta_se"]
+            out.update(z=z, p_value=math.erfc(abs(z) / math.sqrt(2.0)))
+    return out
+
+
 class DeviceMetrics:
     """Streaming exact ROC-AUC + log-loss of up to ``capacity`` samples held as keys on ``device``;
     ``grouped``: also their group ids, for the per-group AUC."""
@@ -152,6 +232,8 @@ class DeviceMetrics:
         self._table_rows: Optional[int] = None             # its G; None: stale
         self._cws: Optional[torch.Tensor] = None           # calibration(): workspace and table
         self._ctab: Optional[torch.Tensor] = None
+        self._pws: Optional[torch.Tensor] = None           # placements(): workspace and the uint32 placements
+        self._place: Optional[torch.Tensor] = None
 
     def _new_rec(self) -> torch.Tensor:
         return torch.zeros(_REC + (_lib.FBN_GAUC_REC_WORDS if self.grouped else 0), dtype=torch.int64, device=self.device)
@@ -364,3 +446,95 @@ class DeviceMetrics:
         bins = self._check_bins(bins)
         keys, n, rec, gids = self._gather(group, stage_on_cpu)
         return self._reduce(keys, n, rec, gids), self._calibrate(keys, n, rec, bins)
+
+    # ------------------------------------------------------------------ DeLong
+    def _place_into(self, keys: torch.Tensor, n: int, rec: torch.Tensor) -> torch.Tensor:
+        """fbn_auc_place over keys[:n] into this instance's placement buffer (the uint32 words as int32)."""
+        need = int(call("fbn_auc_place_workspace_size", n))
+        if self._pws is None or self._pws.numel() < need:
+            self._pws = None
+            self._pws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if self._place is None or self._place.numel() < n:
+            self._place = None
+            self._place = torch.empty(max(1, n), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            call("fbn_auc_place", keys.data_ptr(), n, self._pws.data_ptr(), self._pws.numel(), self._place.data_ptr(),
+                 rec.data_ptr() + 32, _lib.stream_handle(self.device))
+        return self._place
+
+    def placements(self) -> torch.Tensor:
+        """The DeLong placement of every sample held, in the samples' own order (int64 device tensor of
+        length ``count``): for a positive 2 * #negatives with a smaller score + #negatives with an equal
+        score, for a negative 2 * #positives with a larger score + #positives with an equal score.  Their
+        sum over either class is compute()'s U2.  The samples stay; bad values surface in compute() /
+        auc_ci(), not here (no host read)."""
+        place = self._place_into(self.keys, self.count, self.rec)
+        return place[:self.count].to(torch.int64) & 0xFFFFFFFF
+
+    def _delong_record(self, keys: torch.Tensor, n: int, rec: torch.Tensor):
+        place = self._place_into(keys, n, rec)
+        out = torch.empty(_lib.FBN_DELONG_REC_WORDS + 1, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            call("fbn_delong_reduce", keys.data_ptr(), place.data_ptr(), keys.data_ptr(), place.data_ptr(), n,
+                 out.data_ptr(), rec.data_ptr() + 32, _lib.stream_handle(self.device))
+        return out
+
+    def _auc_ci(self, keys: torch.Tensor, n: int, rec: torch.Tensor, level: float) -> Dict:
+        host = self._delong_record(keys, n, rec).cpu().numpy()      # the one device-to-host read: record + status
+        self._check_status(int(host[-1]))
+        record = [int(v) for v in host[:-1]]
+        out = delong_from_record(record, level=level)
+        out["record"] = record
+        return out
+
+    def auc_ci(self, level: float = 0.95, group=None, stage_on_cpu: bool = False) -> Dict:
+        """DeLong's standard error and confidence interval of the AUC of the samples held (they stay):
+        delong_from_record()'s {"auc", "auc_var", "auc_se", "ci_lo", "ci_hi", "level", "n", "n_pos"} plus
+        "record", the 8 exact integers behind them.  One sort, one 72-byte read; independent of the
+        samples' order, the update sizes and the rank split.  NaN (not an error) with fewer than 2
+        samples of a class.  Raises the ValueError compute() raises for the same status word.
+        group / stage_on_cpu: as in compute() (the same all-gather)."""
+        level = _check_level(level)
+        keys, n, rec, _ = self._gather(group, stage_on_cpu)
+        return self._auc_ci(keys, n, rec, level)
+
+
+def compare_auc(a: DeviceMetrics, b: DeviceMetrics, level: float = 0.95, group=None, stage_on_cpu: bool = False) -> Dict:
+    """DeLong's paired test of two AUCs: ``a`` and ``b`` were fed the SAME samples in the same order (two
+    checkpoints, compute modes or epochs over one validation split).  Returns delong_from_record()'s
+    three-record dict -- a's interval plus {"auc_a", "auc_b", "delta", "cov", "delta_var", "delta_se",
+    "z", "p_value"} -- and "records": {"aa", "bb", "ab"}, the exact integers.  Two sorts, three
+    reduces, one read.  Unequal counts raise ValueError before any launch; labels that differ at any
+    sample raise it after the read, as do the status bits compute() reports.  group: collective; both
+    instances' keys are all-gathered in rank-major order, which keeps the pairs aligned."""
+    level = _check_level(level)
+    if a.count != b.count:
+        raise ValueError(f"compare_auc needs the same samples in both: a holds {a.count}, b holds {b.count}")
+    if a.device != b.device:
+        raise ValueError(f"compare_auc: a is on {a.device}, b on {b.device}")
+    ka, n, rec_a, _ = a._gather(group, stage_on_cpu)
+    kb, nb, rec_b, _ = b._gather(group, stage_on_cpu)
+    if n != nb:
+        raise ValueError(f"compare_auc needs the same samples in both: a holds {n} over the group, b holds {nb}")
+    W = _lib.FBN_DELONG_REC_WORDS + 1
+    pa, pb = a._place_into(ka, n, rec_a), b._place_into(kb, n, rec_b)
+    out = torch.empty(3 * W, dtype=torch.int64, device=a.device)
+    pair = torch.zeros(2, dtype=torch.int32, device=a.device)      # the pair's own status word: the label mismatch
+    with torch.cuda.device(a.device):
+        st = _lib.stream_handle(a.device)
+        call("fbn_delong_reduce", ka.data_ptr(), pa.data_ptr(), ka.data_ptr(), pa.data_ptr(), n,
+             out.data_ptr(), rec_a.data_ptr() + 32, st)
+        call("fbn_delong_reduce", kb.data_ptr(), pb.data_ptr(), kb.data_ptr(), pb.data_ptr(), n,
+             out.data_ptr() + 8 * W, rec_b.data_ptr() + 32, st)
+        call("fbn_delong_reduce", ka.data_ptr(), pa.data_ptr(), kb.data_ptr(), pb.data_ptr(), n,
+             out.data_ptr() + 16 * W, pair.data_ptr(), st)
+    host = out.cpu().numpy().reshape(3, W)       # the one device-to-host read: three records + status words
+    a._check_status(int(host[0, -1]))
+    b._check_status(int(host[1, -1]))
+    if int(host[2, -1]) & _PAIR_STATUS:
+        raise ValueError("compare_auc: the labels of a and b differ at some sample (label mismatch): the two "
+                         "were not fed the same samples in the same order")
+    recs = {k: [int(v) for v in host[r, :-1]] for r, k in enumerate(("aa", "bb", "ab"))}
+    res = delong_from_record(recs["aa"], recs["bb"], recs["ab"], level=level)
+    res["records"] = recs
+    return res

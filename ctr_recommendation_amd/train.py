@@ -85,7 +85,9 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
     "valid_logloss": [per epoch], "trainer"}; with the model-config key ``valid_group_by`` (a batch
     column, e.g. user_id) also "valid_gauc": [per epoch] and a `` | Valid GAUC: `` field on the epoch line;
     with ``valid_calibration_bins`` (B in [1, 1024]) also "valid_ece", "valid_pcoc", "valid_ne": [per epoch]
-    and `` | Valid ECE: ... | PCOC: ... | NE: ... `` on the epoch line.
+    and `` | Valid ECE: ... | PCOC: ... | NE: ... `` on the epoch line; with ``valid_auc_ci`` (true, or a
+    level in (0, 1)) also "valid_auc_se": [per epoch], DeLong's standard error of the validation AUC, and
+    `` | AUC SE: 0.0012`` on the epoch line.
 
     Full-state checkpoints (checkpoint.py; also the model-config keys ``resume_from``,
     ``checkpoint_every_steps``, ``state_dir``): save_every: one every that many optimizer steps and at
@@ -130,7 +132,11 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
     valid_gauc = []
     calib_bins = model_cfg.get("valid_calibration_bins")  # e.g. 10: also report the calibration of the probabilities
     valid_ece, valid_pcoc, valid_ne = [], [], []
+    auc_ci = model_cfg.get("valid_auc_ci")                # true or a level: also report DeLong's standard error of the AUC
+    valid_auc_se = []
     ev_args = {}
+    if auc_ci:
+        ev_args["auc_ci"] = auc_ci
     if group_by:
         ev_args["group_by"] = str(group_by)
     if calib_bins:
@@ -143,7 +149,7 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
     if saving and not state_dir:
         state_dir = resume or os.path.join("..", "checkpoints", "state")
     lists = {"valid_logloss": valid_logloss, "valid_gauc": valid_gauc, "valid_ece": valid_ece,
-             "valid_pcoc": valid_pcoc, "valid_ne": valid_ne}
+             "valid_pcoc": valid_pcoc, "valid_ne": valid_ne, "valid_auc_se": valid_auc_se}
 
     def save_state(epoch: int, steps: int, loss_sum: float) -> None:
         """The run as it stands: `steps` steps of (0-based) `epoch` done, their losses summing to loss_sum."""
@@ -161,7 +167,7 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
         best_auc = float(extra["best_auc"])
         history += [tuple(h) for h in extra["history"]]
         for k, v in lists.items():
-            v += list(extra["lists"][k])
+            v += list(extra["lists"].get(k, []))          # a list added after the state was saved: empty
         train_loader.load_state_dict(extra["loader"], skip=start_steps)
         log0(f"Resumed from {resume} | Epoch {start_epoch + 1} | Step {start_steps} | "
              f"LR: {trainer.current_lr():.6f}")
@@ -228,6 +234,10 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
             valid_ne.append(ne)
             fmt = lambda v: v if v is None else f"{v:.4f}"            # noqa: E731
             line += f" | Valid ECE: {fmt(ece)} | PCOC: {fmt(pcoc)} | NE: {fmt(ne)}"
+        if auc_ci:
+            se = float(ev["auc_se"]) if len(valid_loader) else None
+            valid_auc_se.append(se)
+            line += f" | AUC SE: {se if se is None else f'{se:.4f}'}"
         log0(line)
         if auc is not None and auc > best_auc:
             best_auc = auc
@@ -250,6 +260,8 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
         out["valid_gauc"] = valid_gauc
     if calib_bins:
         out.update(valid_ece=valid_ece, valid_pcoc=valid_pcoc, valid_ne=valid_ne)
+    if auc_ci:
+        out["valid_auc_se"] = valid_auc_se
     return out
 
 

@@ -1223,7 +1223,7 @@ class FiBiNETTrainer:
 
     @torch.no_grad()
     def evaluate(self, loader_or_batches, metrics=None, group_by: Optional[str] = None,
-                 calibration_bins: Optional[int] = None) -> Dict:
+                 calibration_bins: Optional[int] = None, auc_ci=None) -> Dict:
         """Validation metrics of (batch, labels) pairs without a per-batch host transfer: predict()'s
         eval-mode forward per batch, its probabilities packed straight into a metrics.DeviceMetrics
         (one launch per batch), then one exact device reduce and one 40-byte read.  Returns
@@ -1238,9 +1238,14 @@ class FiBiNETTrainer:
         calibration_bins: an integer B in [1, 1024]: the result also holds {"ece", "mce", "ece_mass",
         "pcoc", "brier", "ne"} and "calibration", DeviceMetrics.calibration(B)'s dict (the reliability
         table in equal-width and equal-mass bins); ne = logloss / entropy of the base rate.  The keys are
-        gathered once for both reduces at N > 1."""
-        from .metrics import DeviceMetrics, normalized_entropy
+        gathered once for every reduce asked at N > 1.
+        auc_ci: a level in (0, 1), or True for 0.95: the result also holds {"auc_se", "auc_ci_lo",
+        "auc_ci_hi", "auc_ci_level"}, DeLong's standard error and interval of the AUC
+        (DeviceMetrics.auc_ci(); NaN with fewer than 2 samples of a class)."""
+        from .metrics import DeviceMetrics, _check_level, normalized_entropy
         grouped = group_by is not None
+        if auc_ci is not None:
+            auc_ci = _check_level(0.95 if auc_ci is True else auc_ci)
         if calibration_bins is not None:
             calibration_bins = DeviceMetrics._check_bins(calibration_bins)
         if metrics is None:
@@ -1263,12 +1268,16 @@ class FiBiNETTrainer:
         group = None
         if self.world > 1:
             group = self.group if self.group is not None else dist.group.WORLD
-        if calibration_bins is None:
-            return metrics.compute(group=group, stage_on_cpu=self.stage_on_cpu)
-        out, cal = metrics.compute_and_calibrate(calibration_bins, group=group, stage_on_cpu=self.stage_on_cpu)
-        out.update({k: cal[k] for k in ("ece", "mce", "ece_mass", "pcoc", "brier")})
-        out["ne"] = normalized_entropy(out["logloss"], cal["n"], cal["n_pos"])
-        out["calibration"] = cal
+        keys, n, rec, gids = metrics._gather(group, self.stage_on_cpu)       # once, for every reduce asked
+        out = metrics._reduce(keys, n, rec, gids)
+        if calibration_bins is not None:
+            cal = metrics._calibrate(keys, n, rec, calibration_bins)
+            out.update({k: cal[k] for k in ("ece", "mce", "ece_mass", "pcoc", "brier")})
+            out["ne"] = normalized_entropy(out["logloss"], cal["n"], cal["n_pos"])
+            out["calibration"] = cal
+        if auc_ci is not None:
+            ci = metrics._auc_ci(keys, n, rec, auc_ci)
+            out.update(auc_se=ci["auc_se"], auc_ci_lo=ci["ci_lo"], auc_ci_hi=ci["ci_hi"], auc_ci_level=ci["level"])
         return out
 
     def check_ids(self) -> None:

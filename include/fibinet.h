@@ -692,7 +692,8 @@ int fbn_eval_reduce(const uint32_t* keys, long long n, void* ws, size_t ws_bytes
  * The reference has no device sort (its only ordering is the host argsort inside roc_auc_score,
  * src/utils.py:18-27).  fbn_sort_u64: out[0 .. n) = in[0 .. n) ascending by the low `bits` bits
  * (1 .. 64); the bits above them must be equal across the keys (they are carried, not compared: the
- * last pass's digit may reach into them).  LSD radix, 8 bits per pass, ceil(bits / 8) passes: the
+ * last pass's digit may reach into them; with bits a multiple of 8 it does not, and the bits above
+ * are a payload that travels with its key: the sort is stable).  LSD radix, 8 bits per pass, ceil(bits / 8) passes: the
  * host picks bits, so the launch sequence is known without a device round trip.  in is not modified
  * and must not overlap out; 0 <= n < 2^31 (else FBN_ERR_ARG, checked on the host before any device
  * work); n == 0 launches nothing.  ws: >= fbn_sort_u64_workspace_size(n) bytes (host-only query),
@@ -771,6 +772,43 @@ int fbn_gauc_reduce(const uint32_t* keys, const uint32_t* gids, long long n, voi
 size_t fbn_calib_workspace_size(long long n);
 int fbn_calib_reduce(const uint32_t* keys, long long n, int bins, void* ws, size_t ws_bytes, uint64_t* out,
                      unsigned* status, void* stream);
+
+/* ---------------------------------------------------------------- device metrics: DeLong placements and sums
+ * The reference reports one AUC per epoch (roc_auc_score, src/utils.py:18-27) and nothing about its
+ * noise: how much of a difference between two checkpoints is chance, a user has to work out on the host
+ * from every probability (src/train_fibinet.py:133-146).  DeLong's estimator gives the variance of an AUC,
+ * and the covariance of two AUCs over the same samples, from one pass; here as exact integers over the
+ * keys fbn_eval_pack wrote.  With m positives and n_neg negatives, the placement of a sample is
+ *   positive i: a_i = 2 * #negatives with a smaller score + #negatives with an equal score   (<= 2 n_neg)
+ *   negative j: b_j = 2 * #positives with a larger score  + #positives with an equal score   (<= 2 m)
+ * so sum a_i = sum b_j = fbn_eval_reduce's U2, and DeLong's components are a_i / (2 n_neg), b_j / (2 m).
+ * fbn_auc_place over keys[0 .. n), 0 <= n < 2^31: place_out[i] (uint32, 4-B aligned) = the placement of
+ * sample i, in the samples' own order.  keys is not modified; a key above (0x3F800000 << 1) | 1 is
+ * counted as 1.0 and sets bit 3 of *status.  One sort of (key, index) pairs (fbn_sort_u64, the index
+ * carried above the 32 compared bits), one prefix sum of the negative flags, two binary searches per
+ * sample along the sorted array, one 4-byte store per sample.  n == 0 launches nothing.  ws: >=
+ * fbn_auc_place_workspace_size(n) bytes (host-only query), 16-B aligned.  A null pointer, n < 0 or
+ * n >= 2^31 and a small or misaligned ws return FBN_ERR_ARG before any device work.  No host sync, no
+ * allocation.
+ * fbn_delong_reduce over two key sets and their placements, [0 .. n) each, the same samples in the same
+ * order (the variance of one set: b = a): out = FBN_DELONG_REC_WORDS uint64 (8-B aligned; zeroed by the call)
+ *     0 n_pos   1 n_neg   2 sum over the positives of place_a   3 ... of place_b
+ *     4, 5 sum over the positives of the low / the high 32 bits of place_a * place_b
+ *     6, 7 the same over the negatives
+ *   followed by one word out[8]: the value of *status after this reduce (one copy reads both).
+ *   The class of sample i is bit 0 of keys_a[i]; where bit 0 of keys_b[i] differs, bit 17 of *status is
+ *   set and the reduce still finishes.  A product is below 2^64 and a sum of them can pass it: the sum of
+ *   the products is words[4] + (words[5] << 32), each word below 2^63 for n < 2^31.  Integer atomics only,
+ *   one per workgroup and word: independent of any order.  n == 0 writes zeros (and the status word).
+ *   A null out / status, a null array with n > 0, n < 0 or n >= 2^31 return FBN_ERR_ARG before any device
+ *   work.  No workspace, no host sync, no allocation. */
+#define FBN_DELONG_REC_WORDS 8
+size_t fbn_auc_place_workspace_size(long long n);
+int fbn_auc_place(const uint32_t* keys, long long n, void* ws, size_t ws_bytes, uint32_t* place_out,
+                  unsigned* status, void* stream);
+int fbn_delong_reduce(const uint32_t* keys_a, const uint32_t* place_a, const uint32_t* keys_b,
+                      const uint32_t* place_b, long long n, unsigned long long* out, unsigned* status,
+                      void* stream);
 
 /* ---------------------------------------------------------------- serving: catalogue scoring + top-K
  * Replaces the per-row scoring loop of src/Prediction.py:106-113 when the rows are the U x M pairs
