@@ -168,6 +168,9 @@ SIGNATURES = {
     "fbn_rec_fields_list": (I, [P, P, P, P, P, P, I, P, LL, P, P, P, P, I, P, P, P, I, I, P, P, I, P, I, I, I, I, I, P]),
     "fbn_rec_topk_list": (I, [P, I, I, I, P, I, I, P, P, I, I, I, P, P, SZ, P, P, P, P, P, P, P]),
     "fbn_rec_rank_list": (I, [P, I, I, I, P, I, I, P, P, I, I, P, P, P, P, P]),
+    "fbn_knn_normalize": (I, [P, I, P, LL, P, I, I, P, P]),
+    "fbn_knn_query_pool": (I, [P, I, I, P, LL, P, I, I, P, P, P]),
+    "fbn_knn_scores": (I, [P, I, P, P, I, I, I, I, I, P, P]),
     "fbn_plan_create": (I, [P]),
     "fbn_plan_destroy": (I, [P]),
     "fbn_plan_size": (I, [P]),

@@ -21,6 +21,12 @@ slot -- scoring only the listed pairs (``fbn_rec_fields_list`` reads the pair's 
 through the list; the selection and rank keys carry the slot, so ties go to the caller's own order),
 and ``evaluate_sampled`` ranks each held-out item against sampled negatives through them.
 
+``similar_items`` / ``retrieve`` / ``recommend`` / ``evaluate_retrieval`` are the retrieval stage in
+front of those lists (csrc/retrieve.hip): cosine similarity between L2-normalised item vectors of one
+``space`` -- the content vectors, the item cache or the id table -- as exact f32 scores, chunk by chunk
+into the same ``fbn_rec_topk`` / ``fbn_rec_rank``; a user's query is the normalised sum of its history
+items' vectors, which ranks as the mean cosine to them does.
+
 Single device, bilinear "all"; a row-sharded table is out of scope.
 """
 from __future__ import annotations
@@ -36,6 +42,9 @@ K_MAX = 256          # include/fibinet.h: fbn_rec_topk
 L_MAX = 32
 DEFAULT_CHUNK_ROWS = 131072
 CATALOGUE_KEYS = ("item_id", "likes_level", "views_level", "item_emb_d128")
+SPACES = ("content", "mm", "id")            # retrieval vector spaces
+DEFAULT_KNN_CHUNK_BYTES = 64 << 20
+Q_MAX = 65535                               # include/fibinet.h: fbn_knn_scores / fbn_rec_topk
 
 
 def _state_of(state) -> Dict[str, torch.Tensor]:
@@ -69,6 +78,39 @@ def _check_lists(item_seq, candidates, by: str, target_slot=None, k: Optional[in
     return U, int(candidates.shape[1])
 
 
+def _check_knn(space: str, n: Optional[int] = None, *, what: str = "n", by: Optional[str] = None, items=None,
+               item_seq=None) -> int:
+    """The argument checks of the retrieval methods, before anything is launched: -> the number of
+    queries.  Shapes only, so it needs no device."""
+    if space not in SPACES:
+        raise ValueError(f"space must be one of {SPACES}, not {space!r}")
+    if by is not None and by not in ("item_id", "index"):
+        raise ValueError(f"by must be 'item_id' or 'index', not {by!r}")
+    if n is not None and not 1 <= int(n) <= K_MAX:
+        raise ValueError(f"{what} must be in 1..{K_MAX}")
+    if items is not None:
+        if not isinstance(items, torch.Tensor) or items.dim() != 1 or items.is_floating_point():
+            raise ValueError("items must be an integer tensor [Q]")
+        if not 1 <= int(items.shape[0]) <= Q_MAX:
+            raise ValueError(f"items holds {int(items.shape[0])} queries: need 1..{Q_MAX} per call")
+        return int(items.shape[0])
+    if not isinstance(item_seq, torch.Tensor) or item_seq.dim() != 2 or item_seq.is_floating_point():
+        raise ValueError("item_seq must be an integer tensor [U, L]")
+    if not 1 <= int(item_seq.shape[0]) <= Q_MAX:
+        raise ValueError(f"item_seq holds {int(item_seq.shape[0])} users: need 1..{Q_MAX} per call")
+    return int(item_seq.shape[0])
+
+
+def _knn_chunks(M: int, Q: int, chunk_bytes: int):
+    """(first column, columns) of the score chunks [Q, Mc] f32 of at most chunk_bytes: Mc a multiple of
+    1024 (fbn_rec_topk's segment) except in the last chunk, or whatever a smaller budget allows."""
+    mc = max(1, int(chunk_bytes) // (4 * Q))
+    if mc >= 1024:
+        mc -= mc % 1024
+    mc = min(mc, M, 0x7FFFFFFF // Q)
+    return [(m0, min(mc, M - m0)) for m0 in range(0, M, mc)]
+
+
 class Recommender:
     """Scores ``catalogue`` (a dict of ``item_id [M]``, ``likes_level [M]``, ``views_level [M]``,
     ``item_emb_d128 [M, 128]``) for user histories with the weights of ``state`` (an App. B
@@ -78,7 +120,8 @@ class Recommender:
     ``check_ids()`` turns into the reference's ``IndexError``."""
 
     def __init__(self, state, model_cfg: Dict, catalogue: Dict[str, torch.Tensor], *, device=None,
-                 max_len: int = 20, chunk_rows: Optional[int] = None):
+                 max_len: int = 20, chunk_rows: Optional[int] = None,
+                 knn_chunk_bytes: int = DEFAULT_KNN_CHUNK_BYTES):
         self.device = torch.device(device if device is not None else "cuda")
         if self.device.type != "cuda":
             raise RuntimeError(f"Recommender runs only on a HIP device, not {self.device} (no CPU fallback)")
@@ -90,6 +133,10 @@ class Recommender:
         self.chunk_rows = int(chunk_rows) if chunk_rows is not None else DEFAULT_CHUNK_ROWS
         if self.chunk_rows < 1:
             raise ValueError("chunk_rows must be positive")
+        self.knn_chunk_bytes = int(knn_chunk_bytes)
+        if self.knn_chunk_bytes < 4:
+            raise ValueError("knn_chunk_bytes must hold at least one score")
+        self._knn: Dict[str, torch.Tensor] = {}            # space -> normalised [M, D], built on first use
         honour = bool(model_cfg.get("honour_config", False))
         btype = model_cfg.get("bilinear_type", "all") if honour else "all"
         if btype not in ("all", "each"):
@@ -143,6 +190,8 @@ class Recommender:
             st = _lib.stream_handle(dev)
             self.err.zero_()
             self._acts = {}
+            self._knn.pop("mm", None)                      # the spaces made of weights; "content" stays
+            self._knn.pop("id", None)
             self._wimg: Dict = {}
             self._w16 = None
             hmm = torch.empty((self.M, d), dtype=torch.float32, device=dev)
@@ -507,5 +556,182 @@ class Recommender:
             raise ValueError("Recommender.evaluate_sampled: the logit of a ranked target is NaN")
         result = metrics.compute(ks)
         result["mean_candidates"] = float(n_cand.item()) / result["n"] if result["n"] else 0.0
+        self.check_ids()
+        return result
+
+    # ------------------------------------------------------------------ retrieval
+    def _space(self, space: str, st) -> torch.Tensor:
+        """The L2-normalised [M, D] f32 matrix of a space, built on first use and kept (4 M D bytes)."""
+        xn = self._knn.get(space)
+        if xn is None:
+            if space == "content":
+                x, row_of = self._x, None
+            elif space == "mm":
+                x, row_of = self.cache, None
+            else:
+                x, row_of = self.p["item_emb.weight"], self.cat["item_id"]
+            D = int(x.shape[1])
+            xn = torch.empty((self.M, D), dtype=torch.float32, device=self.device)
+            call("fbn_knn_normalize", ptr(x), D, ptr(row_of), int(x.shape[0]), ptr(xn), self.M, D, ptr(self.err), st)
+            self._knn[space] = xn
+        return xn
+
+    def _knn_topk(self, xn, Q, k, qn, q_pos, seq, L, st) -> Dict[str, torch.Tensor]:
+        """Each query's k most similar catalogue rows through the chunk loop: fbn_knn_scores into
+        fbn_rec_topk.  exclude is always on, so padding items never come back; seq [Q, L] (or None)
+        names the ids to leave out besides."""
+        dev, D = self.device, int(xn.shape[1])
+        carry = torch.zeros((Q, k), dtype=torch.int64, device=dev)
+        out = {"index": torch.empty((Q, k), dtype=torch.int64, device=dev),
+               "item_id": torch.empty((Q, k), dtype=torch.int64, device=dev),
+               "score": torch.empty((Q, k), dtype=torch.float32, device=dev)}
+        prob = torch.empty((Q, k), dtype=torch.float32, device=dev)     # the sigmoid of a cosine: dropped
+        chunks = _knn_chunks(self.M, Q, self.knn_chunk_bytes)
+        S = torch.empty(Q * chunks[0][1], dtype=torch.float32, device=dev)
+        nws = int(_lib.lib().fbn_rec_topk_workspace_size(Q, chunks[0][1], k))
+        ws = torch.empty(max(1, (nws + 7) // 8), dtype=torch.int64, device=dev)
+        for i, (m0, Mc) in enumerate(chunks):
+            call("fbn_knn_scores", ptr(qn), D, ptr(q_pos), ptr(xn), self.M, Q, m0, Mc, D, ptr(S), st)
+            last = i == len(chunks) - 1
+            call("fbn_rec_topk", ptr(S), Q, m0, Mc, ptr(self.cat["item_id"]), ptr(seq), L, 1, k, ptr(carry), ptr(ws),
+                 nws, ptr(out["index"]) if last else None, ptr(out["item_id"]) if last else None,
+                 ptr(out["score"]) if last else None, ptr(prob) if last else None, ptr(self.status), st)
+        return out
+
+    @staticmethod
+    def _blank(out: Dict[str, torch.Tensor], dead: torch.Tensor) -> None:
+        """Rows of queries without a vector become index -1, item_id -1, score -inf (device ops)."""
+        dead = dead[:, None]
+        out["index"] = torch.where(dead, torch.full_like(out["index"], -1), out["index"])
+        out["item_id"] = torch.where(dead, torch.full_like(out["item_id"], -1), out["item_id"])
+        out["score"] = torch.where(dead, torch.full_like(out["score"], float("-inf")), out["score"])
+
+    @torch.no_grad()
+    def similar_items(self, items: torch.Tensor, k: int, *, space: str = "content", by: str = "item_id",
+                      exclude_self: bool = True) -> Dict[str, torch.Tensor]:
+        """The k catalogue items most similar to each query item, best first: ``index`` (catalogue
+        position), ``item_id``, ``score`` (cosine in ``space``, f32), all [Q, k].  ``items`` [Q] holds
+        item ids (``by="item_id"``, mapped by :meth:`positions`) or catalogue positions
+        (``by="index"``); the query vector is read out of the catalogue matrix.  Equal scores go to the
+        smaller position.  Padding items are never returned; ``exclude_self`` leaves out every catalogue
+        row that carries the query's id.  A query that is not in the catalogue gives a row of index -1,
+        item_id -1, score -inf, and with fewer than k eligible items the tail is filled the same way.
+        Nothing is copied to the host and nothing synchronises."""
+        Q = _check_knn(space, k, what="k", by=by, items=items)
+        k, dev = int(k), self.device
+        with torch.cuda.device(dev):
+            st = _lib.stream_handle(dev)
+            xn = self._space(space, st)
+            it = items.to(dev).long()
+            pos = (self.positions(it) if by == "item_id" else it).contiguous()
+            live = (pos >= 0) & (pos < self.M)
+            seq = None
+            if exclude_self:                               # fbn_rec_topk's history rule on a one-slot history
+                own = self.cat["item_id"][pos.clamp(0, self.M - 1)]
+                seq = torch.where(live, own, torch.zeros_like(own)).reshape(Q, 1).contiguous()
+            out = self._knn_topk(xn, Q, k, None, pos, seq, 1 if exclude_self else 0, st)
+            self._blank(out, ~live)
+        return out
+
+    def _queries(self, item_seq: torch.Tensor, xn: torch.Tensor, st):
+        """(seq [U, L] on the device, Qn [U, D], n_used [U]) of the users' histories."""
+        dev, D = self.device, int(xn.shape[1])
+        seq = item_seq.to(dev).long()
+        if seq.shape[1] > self.max_len:
+            seq = seq[:, seq.shape[1] - self.max_len:]         # the collator keeps the last max_len
+        seq = seq.contiguous()
+        U, L = int(seq.shape[0]), int(seq.shape[1])
+        qn = torch.empty((U, D), dtype=torch.float32, device=dev)
+        n_used = torch.empty(U, dtype=torch.int32, device=dev)
+        call("fbn_knn_query_pool", ptr(seq) if L else None, U, L, ptr(self._pos), self.V, ptr(xn), self.M, D,
+             ptr(qn), ptr(n_used), st)
+        return seq, qn, n_used
+
+    @torch.no_grad()
+    def retrieve(self, item_seq: torch.Tensor, n: int, *, space: str = "content",
+                 exclude_history: bool = True) -> Dict[str, torch.Tensor]:
+        """Each user's n nearest catalogue items, best first: ``index``, ``item_id``, ``score`` [U, n]
+        and ``n_used`` [U] (int32), the history slots that made the query.  The query is the normalised
+        sum of the vectors of the history items the catalogue holds (a repeated id counts each time), so
+        ``score`` orders the catalogue as the mean cosine to those items does.  Padding items are never
+        returned, nor -- with ``exclude_history`` -- items of the user's own history.  A user with
+        ``n_used == 0`` has no query and gets an all-empty row (index -1, item_id -1, score -inf): fall
+        back to ``topk(None, k)`` for such users.  ``index`` feeds ``topk_lists(..., by="index")`` as it
+        is (-1 is that API's empty slot).  1 <= n <= 256; no host copy and no sync."""
+        U = _check_knn(space, n, item_seq=item_seq)
+        n, dev = int(n), self.device
+        with torch.cuda.device(dev):
+            st = _lib.stream_handle(dev)
+            xn = self._space(space, st)
+            seq, qn, n_used = self._queries(item_seq, xn, st)
+            L = int(seq.shape[1]) if exclude_history else 0
+            out = self._knn_topk(xn, U, n, qn, None, seq if L else None, L, st)
+            self._blank(out, n_used == 0)
+            out["n_used"] = n_used
+        return out
+
+    @torch.no_grad()
+    def recommend(self, item_seq: torch.Tensor, k: int, *, n_candidates: int = 200, space: str = "content",
+                  exclude_history: bool = True) -> Dict[str, torch.Tensor]:
+        """Two stages: :meth:`retrieve` ``n_candidates`` per user, then :meth:`topk_lists` over them
+        (``by="index"``).  Returns ``topk_lists``' dict; its logits are the eval forward's for those
+        pairs, exactly as ``topk`` gives them.  A user without a usable history gets an all -1 row."""
+        _check_knn(space, n_candidates, what="n_candidates", item_seq=item_seq)
+        if not 1 <= int(k) <= K_MAX:
+            raise ValueError(f"k must be in 1..{K_MAX}")
+        cands = self.retrieve(item_seq, n_candidates, space=space, exclude_history=exclude_history)["index"]
+        return self.topk_lists(item_seq, cands, k, exclude_history=exclude_history, by="index")
+
+    @torch.no_grad()
+    def evaluate_retrieval(self, pairs, ns=(50, 100, 200), *, space: str = "content", exclude_history: bool = True,
+                           max_users: Optional[int] = None, users_per_block: int = 64) -> Dict:
+        """Recall of the retrieval stage on held-out interactions: ``pairs`` and the selection of the
+        positive rows are :meth:`evaluate`'s; each block's [users, M] similarity rows go to
+        ``fbn_rec_rank`` with the held-out item as target, into a :class:`RankMetrics` record.  Returns
+        ``RankMetrics.compute(ns)``: ``hr[n]`` is the share of ranked users whose held-out item is among
+        ``retrieve(n)``'s -- recall@n.  A user with ``n_used == 0`` has no query: its target becomes -1,
+        rank 0, and it is counted in ``n_skipped``.  Ends with ``check_ids()``."""
+        from .rank_metrics import RankMetrics, _check_ks
+        ns = _check_ks(ns)
+        if space not in SPACES:
+            raise ValueError(f"space must be one of {SPACES}, not {space!r}")
+        upb = int(users_per_block)
+        if not 1 <= upb <= Q_MAX:
+            raise ValueError(f"users_per_block must be in 1..{Q_MAX}")
+        left = None if max_users is None else int(max_users)
+        dev = self.device
+        metrics = RankMetrics(dev)
+        with torch.cuda.device(dev):
+            st = _lib.stream_handle(dev)
+            xn = self._space(space, st)
+            D = int(xn.shape[1])
+            for batch, labels in pairs:
+                if left is not None and left <= 0:
+                    break
+                rows = (labels.to(dev).reshape(-1) == 1).nonzero().reshape(-1)      # the per-batch sync
+                if left is not None:
+                    rows = rows[:left]
+                    left -= int(rows.numel())
+                if rows.numel() == 0:
+                    continue
+                seqs, tgts = batch["item_seq"].to(dev)[rows], batch["item_id"].to(dev).reshape(-1)[rows]
+                for r0 in range(0, int(rows.numel()), upb):
+                    seq, qn, n_used = self._queries(seqs[r0:r0 + upb], xn, st)
+                    U, L = int(seq.shape[0]), int(seq.shape[1])
+                    tpos = self.positions(tgts[r0:r0 + upb])
+                    tpos = torch.where(n_used == 0, torch.full_like(tpos, -1), tpos).contiguous()
+                    buf = torch.empty((U, self.M), dtype=torch.float32, device=dev)
+                    chunks = _knn_chunks(self.M, U, self.knn_chunk_bytes)
+                    S = buf if len(chunks) == 1 else torch.empty(U * chunks[0][1], dtype=torch.float32, device=dev)
+                    for m0, Mc in chunks:
+                        call("fbn_knn_scores", ptr(qn), D, None, ptr(xn), self.M, U, m0, Mc, D, ptr(S), st)
+                        if S is not buf:
+                            buf[:, m0:m0 + Mc].copy_(S[:U * Mc].view(U, Mc))
+                    rank = torch.empty(U, dtype=torch.int32, device=dev)
+                    n_el = torch.empty(U, dtype=torch.int32, device=dev)
+                    call("fbn_rec_rank", ptr(buf), self.M, U, self.M, ptr(self.cat["item_id"]), ptr(seq) if L else None,
+                         L, int(bool(exclude_history)), ptr(tpos), ptr(rank), ptr(n_el), ptr(self.status), st)
+                    metrics.update(rank)
+        result = metrics.compute(ns)
         self.check_ids()
         return result

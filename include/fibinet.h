@@ -932,6 +932,38 @@ int fbn_rec_rank_list(const float* logits, int ld, int U, int C, const int64_t* 
                       const int64_t* item_id, const int64_t* item_seq, int L, int exclude,
                       const int64_t* target_slot, int* rank, int* n_eligible, unsigned* status, void* stream);
 
+/* ---------------------------------------------------------------- serving: retrieval (nearest neighbours)
+ * The stage in front of the per-user lists: the reference scores rows it is handed (src/Prediction.py:
+ * 106-113) and has no retrieval of its own.  Cosine similarity between L2-normalised f32 vectors of
+ * length D in {16,32,64,128,256}; selection is fbn_rec_topk / fbn_rec_rank on the scores (their key order,
+ * tie rule, exclusion and carry), nothing here selects.  Rows are 16-byte aligned (ldx, ldq % 4 == 0).
+ *
+ * fbn_knn_normalize: Xn[m] = x / |x|_2 (f32 [M][D]) with x = X[row_of ? row_of[m] : m] (X [n_src][ldx],
+ * ldx >= D); replaces torch.nn.functional.normalize on a gathered copy.  A zero row stays zero (no NaN
+ * from 0/0).  A row index outside [0, n_src) gives a zero row and sets bit 0 of the sticky *err (the
+ * IndexError path of fbn_fields_fwd; nothing faults).  M == 0 launches nothing. */
+int fbn_knn_normalize(const float* X, int ldx, const int64_t* row_of, long long n_src, float* Xn, int M, int D,
+                      int* err, void* stream);
+/* fbn_knn_query_pool: Qn[u] (f32 [U][D]) = the normalised sum, in slot order, of Xn[pos_of_id[id]] over the
+ * slots of item_seq[u] ([U][L], 0 <= L <= 32; NULL: no slots) whose id is not 0, lies in [0, V) and has
+ * pos_of_id[id] in [0, M) (pos_of_id [V] int32: id -> catalogue position, negative for an id the
+ * catalogue lacks); n_used[u] (int32) = the slots summed, a repeated id counting each time as in the
+ * model's own history mean.  No usable slot: Qn[u] = 0, n_used[u] = 0.  <Qn[u], Xn[m]> is the mean cosine
+ * between item m and the history items times one positive factor per user, so it ranks as the mean does. */
+int fbn_knn_query_pool(const int64_t* item_seq, int U, int L, const int* pos_of_id, long long V, const float* Xn,
+                       int M, int D, float* Qn, int* n_used, void* stream);
+/* fbn_knn_scores: S[q * Mc + j] = sum_k a_q[k] * Xn[m0 + j][k] for 0 <= j < Mc (f32 [Q][Mc]: the logits
+ * argument of fbn_rec_topk for the chunk [m0, m0 + Mc), or one chunk of fbn_rec_rank's row); replaces a
+ * torch.matmul of the two normalised matrices.  q_pos == NULL: a_q = Qn[q * ldq ..] (ldq >= D).
+ * Otherwise a_q = Xn[q_pos[q]] -- an item query read straight out of the catalogue matrix -- or the zero
+ * vector when q_pos[q] is outside [0, M) (its row of S is exactly 0).  Exact f32 on
+ * v_mfma_f32_32x32x2_f32: every score is one fmaf chain in ascending k, so its bits depend on its two
+ * vectors only -- not on Q, the chunk or the other queries -- and <a, b> == <b, a>.  m0 >= 0,
+ * m0 + Mc <= M, Q <= 65535 and Q * Mc < 2^31 (fbn_rec_topk's limits; else FBN_ERR_ARG, checked on the
+ * host before any device work); Q == 0 or Mc == 0 launches nothing. */
+int fbn_knn_scores(const float* Qn, int ldq, const int64_t* q_pos, const float* Xn, int M, int Q, int m0, int Mc,
+                   int D, float* S, void* stream);
+
 /* ---------------------------------------------------------------- step programs (native step driver)
  * Replaces the Python loop body that issues one training step (src/train_fibinet.py:113-123): the
  * host records a step's calls of this library -- entry point, arguments, and the cross-stream

@@ -26,6 +26,15 @@ d = 128, once in fp32 and once in bf16:
 per call, the two routes interleaved after a warm-up; a run times several back-to-back calls with one
 HIP event pair so the window is not a single short call.  No threshold: the two figures and their
 ratio, written to profiles/recommend_lists.json.
+
+--retrieve: the two-stage path at the first leg's shape (d = 128, bf16, M = 91,718, U = 64,
+L = 20, K = 10), same method:
+  (a) topk_ms        Recommender.topk(k = 10) over the whole catalogue
+  (b) recommend_ms   Recommender.recommend(k = 10, n_candidates = 200): retrieval in the content space,
+                     then topk_lists over each user's 200
+and fbn_knn_scores alone at Q = 64 and Q = 8192 over the whole catalogue beside fbn_gemm (fp32, transB)
+on the same normalised operands (back-to-back calls per timed run, the two interleaved), with the largest
+difference between their outputs.  Written to profiles/retrieve_two_stage.json.
 """
 import argparse
 import json
@@ -206,6 +215,102 @@ def lists_bench(args):
     print(json.dumps(res))
 
 
+def retrieve_bench(args, rec, seq):
+    """--retrieve: topk vs recommend, then fbn_knn_scores vs fbn_gemm on the same operands."""
+    import ctr_recommendation_amd.recommend as rmod
+    dev, U, K, M = rec.device, seq.shape[0], args.k, rec.M
+    n_cand, space = args.candidates, "content"
+
+    def full():
+        return rec.topk(seq, K)
+
+    def two_stage():
+        return rec.recommend(seq, K, n_candidates=n_cand, space=space)
+
+    full(), two_stage()                                     # warm-up (allocations, bf16 images, the space)
+    ta, tb = [], []
+    for _ in range(args.runs):                              # interleaved A/B
+        t, ra = _timed(full)
+        ta.append(t)
+        t, rb = _timed(two_stage)
+        tb.append(t)
+    rec.check_ids()
+    # how much of the full sweep's top K the shortlist kept (random weights and vectors: a property of
+    # this synthetic input, not of any model)
+    overlap = sum(len(set(ra["index"][u].tolist()) & set(rb["index"][u].tolist())) for u in range(U)) / (U * K)
+
+    # one probed run of (b): kernel spans per stage
+    stages = {}
+    call0 = rmod.call
+
+    def probed_call(name, *a):
+        if name.startswith("fbn_knn_") or name in ("fbn_rec_topk", "fbn_rec_topk_list"):
+            kp = _lib.KernelProbe()
+            stages.setdefault(name, []).append((kp, None))
+            try:
+                return call0(name, *a)
+            finally:
+                kp.done()
+        return call0(name, *a)
+
+    rmod.call = probed_call
+    two_stage()
+    torch.cuda.synchronize()
+    rmod.call = call0
+    stage_ms = {k[4:]: round(_span(v), 4) for k, v in stages.items()}
+
+    # the scores kernel alone beside fbn_gemm on the same normalised operands
+    st = _lib.stream_handle(dev)
+    xn = rec._space(space, st)
+    D = int(xn.shape[1])
+    g = torch.Generator().manual_seed(11)
+    kernels = {}
+    for Q, calls in ((64, 20), (8192, 1)):
+        q = torch.randn((Q, D), generator=g)
+        qn = (q / q.norm(dim=1, keepdim=True)).to(dev).contiguous()
+        Sa = torch.empty((Q, M), dtype=torch.float32, device=dev)
+        Sb = torch.empty((Q, M), dtype=torch.float32, device=dev)
+
+        def knn():
+            for _ in range(calls):
+                _lib.call("fbn_knn_scores", _lib.ptr(qn), D, None, _lib.ptr(xn), M, Q, 0, M, D, _lib.ptr(Sa), st)
+
+        def gemm():
+            for _ in range(calls):
+                ops.gemm(qn, xn, Sb, Q, M, D, D, D, M, False, True, stream=st)
+
+        knn(), gemm()
+        ka, kb = [], []
+        for _ in range(args.runs):
+            ka.append(_timed(knn)[0] / calls)
+            kb.append(_timed(gemm)[0] / calls)
+        ma, mb = statistics.median(ka), statistics.median(kb)
+        kernels[f"Q{Q}"] = {"calls_per_run": calls, "knn_scores_ms": round(ma, 4), "gemm_fp32_ms": round(mb, 4),
+                            "ratio_gemm_over_knn": round(mb / ma, 3),
+                            "knn_scores_ms_min_max": [round(min(ka), 4), round(max(ka), 4)],
+                            "gemm_fp32_ms_min_max": [round(min(kb), 4), round(max(kb), 4)],
+                            "knn_gbytes_per_s": round((4.0 * M * D + 4.0 * Q * M) / ma / 1e6, 1),
+                            "knn_tflops": round(2.0 * Q * M * D / ma / 1e9, 2),
+                            "max_abs_diff_vs_gemm": (Sa - Sb).abs().max().item()}
+        del Sa, Sb
+
+    ma, mb = statistics.median(ta), statistics.median(tb)
+    res = {"device": torch.cuda.get_device_name(dev), "users": U, "items": M, "k": K, "d": rec.d, "dtype": args.dtype,
+           "space": space, "space_dim": D, "n_candidates": n_cand, "runs": args.runs,
+           "statistic": "median of runs (HIP events, one process, the two routes interleaved)",
+           "topk_ms": round(ma, 3), "recommend_ms": round(mb, 3), "ratio_topk_over_recommend": round(ma / mb, 2),
+           "topk_ms_min_max": [round(min(ta), 3), round(max(ta), 3)],
+           "recommend_ms_min_max": [round(min(tb), 3), round(max(tb), 3)],
+           "pairs_scored": {"topk": U * M, "recommend": U * n_cand},
+           "recommend_stage_kernel_ms": stage_ms, "topk_overlap_on_random_input": round(overlap, 4),
+           "scores_kernel": kernels}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--users", type=int, default=64)
@@ -220,10 +325,13 @@ def main():
     ap.add_argument("--lists", action="store_true", help="time topk_lists on per-user shortlists against topk")
     ap.add_argument("--slots", type=int, default=500, help="--lists: slots per user")
     ap.add_argument("--list-calls", type=int, default=20, help="--lists: topk_lists calls per timed run")
+    ap.add_argument("--retrieve", action="store_true", help="time recommend (retrieve + topk_lists) against topk")
+    ap.add_argument("--candidates", type=int, default=200, help="--retrieve: shortlist length per user")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join("profiles", "recommend_lists.json" if args.lists else
+                                "retrieve_two_stage.json" if args.retrieve else
                                 "recommend_rank_eval.json" if args.rank_eval else "recommend_vs_expanded.json")
     if args.lists:
         return lists_bench(args)
@@ -240,6 +348,8 @@ def main():
     seq[torch.rand((U, L), generator=g) < 0.3] = 0
     seq = seq.to(dev)
     rec = Recommender(model.state_dict(), cfg, cat, device=dev, chunk_rows=args.chunk_rows)
+    if args.retrieve:
+        return retrieve_bench(args, rec, seq)
     if args.rank_eval:
         return rank_eval(args, rec, seq, torch.randint(0, M, (U,), generator=g).to(dev))
     catd = {k: v.to(dev) for k, v in rec.cat.items()}
