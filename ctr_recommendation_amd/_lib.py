@@ -155,6 +155,10 @@ SIGNATURES = {
     "fbn_gauc_reduce": (I, [P, P, LL, P, SZ, P, P, P, P]),
     "fbn_calib_workspace_size": (SZ, [LL]),
     "fbn_calib_reduce": (I, [P, LL, I, P, SZ, P, P, P]),
+    "fbn_isotonic_workspace_size": (SZ, [LL]),
+    "fbn_isotonic_max_blocks": (LL, [LL]),
+    "fbn_isotonic_fit": (I, [P, LL, P, SZ, P, LL, P, P]),
+    "fbn_isotonic_apply": (I, [P, LL, P, I, P, P]),
     "fbn_auc_place_workspace_size": (SZ, [LL]),
     "fbn_auc_place": (I, [P, LL, P, SZ, P, P, P]),
     "fbn_delong_reduce": (I, [P, P, P, P, LL, P, P, P]),

@@ -21,9 +21,14 @@ depend on the samples' order, on the update sizes or on the rank split.
 ``calibration(bins)`` is the other half of validation (§20): the reliability table of the samples held, in
 equal-width and in equal-mass bins, as exact integers from one device sort and one prefix sum, and the
 ECE / MCE / PCOC / Brier score derived from it on the host with Python integers.
+
+``isotonic()`` closes the loop (§25): the exact isotonic fit of the samples held, as an
+:class:`IsotonicCalibrator` -- a monotone map applied on the device (``cal(probs)``) and saved as the
+integers it is made of.
 """
 from __future__ import annotations
 
+import json
 import math
 import statistics
 from fractions import Fraction
@@ -205,6 +210,131 @@ def delong_from_record(rec_aa, rec_bb=None, rec_ab=None, level: float = 0.95) ->
     return out
 
 
+_ISO_MODES = {"interp": 0, "step": 1}
+_ISO_ONE_BITS = 0x3F800000                       # bits(1.0f): a key's score bits are at most this
+
+
+class IsotonicCalibrator:
+    """The exact isotonic fit of a set of (probability, label) samples (csrc/isotonic.hip):
+    K blocks of consecutive scores [lo_j, hi_j] with n_j samples, n_pos_j of them positive; the block
+    values n_pos_j / n_j increase strictly and lo_j <= hi_j < lo_{j+1}.  ``cal(probs)`` maps fp32
+    probabilities on the device: a score inside a block gets the block's value, a score between two
+    blocks the linear interpolation (``mode="step"``: the value of the next block up), a score below
+    (above) every block the first (last) value -- sklearn's IsotonicRegression(out_of_bounds="clip").
+    The map is non-decreasing, so a ranking changes by new ties only.
+
+    ``blocks``: numpy lo, hi (float32) and n, n_pos (int64); ``table``: the device tensor the apply
+    kernel reads (int64 words: K, then bits(lo) | bits(hi) << 32 and n | n_pos << 32 per block).
+    Built by DeviceMetrics.isotonic(), from_dict() or load(); to_dict() / save() hold integers only."""
+
+    def __init__(self, blocks: Dict, device=None):
+        lo = np.ascontiguousarray(blocks["lo"], dtype=np.float32).reshape(-1)
+        hi = np.ascontiguousarray(blocks["hi"], dtype=np.float32).reshape(-1)
+        n = np.ascontiguousarray(blocks["n"], dtype=np.int64).reshape(-1)
+        n_pos = np.ascontiguousarray(blocks["n_pos"], dtype=np.int64).reshape(-1)
+        K = len(n)
+        if K == 0:
+            raise ValueError("IsotonicCalibrator: no blocks (fitted on no sample)")
+        if not (len(lo) == len(hi) == len(n_pos) == K):
+            raise ValueError("IsotonicCalibrator: lo, hi, n and n_pos differ in length")
+        lb, hb = lo.view(np.uint32).astype(np.int64), hi.view(np.uint32).astype(np.int64)
+        if lb.max() > _ISO_ONE_BITS or hb.max() > _ISO_ONE_BITS:
+            raise ValueError("IsotonicCalibrator: a block score lies outside [0, 1]")
+        if np.any(lb > hb) or np.any(hb[:-1] >= lb[1:]):
+            raise ValueError("IsotonicCalibrator: the blocks are unsorted or overlap (need lo_j <= hi_j < lo_{j+1})")
+        if np.any(n < 1) or np.any(n_pos < 0) or np.any(n_pos > n) or int(n.sum()) > _MAX_N:
+            raise ValueError("IsotonicCalibrator: need 1 <= n_j, 0 <= n_pos_j <= n_j and fewer than 2^31 samples")
+        if any(int(n_pos[j]) * int(n[j + 1]) >= int(n_pos[j + 1]) * int(n[j]) for j in range(K - 1)):
+            raise ValueError("IsotonicCalibrator: the block values n_pos / n do not increase strictly")
+        self.blocks = {"lo": lo, "hi": hi, "n": n, "n_pos": n_pos}
+        for v in self.blocks.values():
+            v.setflags(write=False)
+        words = np.empty(2 * K + 1, dtype=np.int64)
+        words[0] = K
+        words[1::2] = lb | (hb << 32)
+        words[2::2] = n | (n_pos << 32)
+        self._words = words
+        self.table: Optional[torch.Tensor] = None
+        self.device: Optional[torch.device] = None
+        if device is not None:
+            self.to(device)
+
+    def __len__(self) -> int:
+        return len(self.blocks["n"])
+
+    @property
+    def values(self) -> np.ndarray:
+        """The block values n_pos / n (float64, strictly increasing)."""
+        return self.blocks["n_pos"].astype(np.float64) / self.blocks["n"].astype(np.float64)
+
+    def to(self, device) -> "IsotonicCalibrator":
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("IsotonicCalibrator applies on a HIP device only (no CPU fallback)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self.table is None or self.device != device:
+            self.table = torch.from_numpy(self._words).to(device)
+            self.device = device
+        return self
+
+    def apply(self, probs: torch.Tensor, mode: str = "interp", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The calibrated probabilities (float32, probs' shape): one launch, no host sync.  ``out``: a
+        contiguous float32 tensor of the same size, or probs itself (in place).  NaN passes through."""
+        if mode not in _ISO_MODES:
+            raise ValueError(f"mode must be 'interp' or 'step', not {mode!r}")
+        _lib.require_hip(probs, "probs")
+        self.to(probs.device)
+        p = probs.detach()
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            if out is probs:
+                raise ValueError("in-place apply needs a contiguous float32 tensor")
+            p = p.to(torch.float32).contiguous()
+        if out is None:
+            out = torch.empty_like(p)
+        else:
+            _lib.require_hip(out, "out")
+            if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != p.numel() or out.device != p.device:
+                raise ValueError("out must be a contiguous float32 tensor of probs' size on probs' device")
+        with torch.cuda.device(self.device):
+            call("fbn_isotonic_apply", p.data_ptr(), p.numel(), self.table.data_ptr(), _ISO_MODES[mode], out.data_ptr(),
+                 _lib.stream_handle(self.device))
+        return out
+
+    __call__ = apply
+
+    def to_dict(self) -> Dict:
+        """Integers only: the score bits and the counts (what save() writes)."""
+        b = self.blocks
+        return {"format": "fibinet-isotonic-1",
+                "lo_bits": [int(v) for v in b["lo"].view(np.uint32)], "hi_bits": [int(v) for v in b["hi"].view(np.uint32)],
+                "n": [int(v) for v in b["n"]], "n_pos": [int(v) for v in b["n_pos"]]}
+
+    @classmethod
+    def from_dict(cls, d: Dict, device=None) -> "IsotonicCalibrator":
+        if not isinstance(d, dict) or d.get("format") != "fibinet-isotonic-1":
+            raise ValueError("not an isotonic calibrator (format 'fibinet-isotonic-1' expected)")
+        cols = []
+        for k in ("lo_bits", "hi_bits", "n", "n_pos"):
+            v = d.get(k)
+            if not isinstance(v, list) or any(isinstance(x, bool) or not isinstance(x, int) or not 0 <= x < (1 << 32) for x in v):
+                raise ValueError(f"isotonic calibrator: {k} must be a list of integers in [0, 2^32)")
+            cols.append(v)
+        lo, hi, n, n_pos = cols
+        return cls({"lo": np.array(lo, dtype=np.uint32).view(np.float32), "hi": np.array(hi, dtype=np.uint32).view(np.float32),
+                    "n": np.array(n, dtype=np.int64), "n_pos": np.array(n_pos, dtype=np.int64)}, device=device)
+
+    def save(self, path: str) -> None:
+        with open(path, "w") as fh:
+            json.dump(self.to_dict(), fh)
+            fh.write("\n")
+
+    @classmethod
+    def load(cls, path: str, device=None) -> "IsotonicCalibrator":
+        with open(path) as fh:
+            return cls.from_dict(json.load(fh), device=device)
+
+
 class DeviceMetrics:
     """Streaming exact ROC-AUC + log-loss of up to ``capacity`` samples held as keys on ``device``;
     ``grouped``: also their group ids, for the per-group AUC."""
@@ -232,6 +362,8 @@ class DeviceMetrics:
         self._table_rows: Optional[int] = None             # its G; None: stale
         self._cws: Optional[torch.Tensor] = None           # calibration(): workspace and table
         self._ctab: Optional[torch.Tensor] = None
+        self._iws: Optional[torch.Tensor] = None           # isotonic(): workspace and table
+        self._itab: Optional[torch.Tensor] = None
         self._pws: Optional[torch.Tensor] = None           # placements(): workspace and the uint32 placements
         self._place: Optional[torch.Tensor] = None
 
@@ -446,6 +578,38 @@ class DeviceMetrics:
         bins = self._check_bins(bins)
         keys, n, rec, gids = self._gather(group, stage_on_cpu)
         return self._reduce(keys, n, rec, gids), self._calibrate(keys, n, rec, bins)
+
+    # ------------------------------------------------------------------ isotonic calibrator
+    def _isotonic(self, keys: torch.Tensor, n: int, rec: torch.Tensor) -> IsotonicCalibrator:
+        need = int(call("fbn_isotonic_workspace_size", n))
+        if self._iws is None or self._iws.numel() < need:
+            self._iws = None
+            self._iws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        words = 2 * int(_lib.lib().fbn_isotonic_max_blocks(n)) + 2
+        if self._itab is None or self._itab.numel() < words:
+            self._itab = torch.empty(words, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            call("fbn_isotonic_fit", keys.data_ptr(), n, self._iws.data_ptr(), self._iws.numel(), self._itab.data_ptr(),
+                 words, rec.data_ptr() + 32, _lib.stream_handle(self.device))
+        host = self._itab[:words].cpu().numpy()  # the one device-to-host read: K, the blocks, the status word
+        K = int(host[0])
+        self._check_status(int(host[1 + 2 * K]))
+        if K == 0:
+            raise ValueError("DeviceMetrics.isotonic: no samples held")
+        ends = host[1:1 + 2 * K:2].copy().view(np.uint32).reshape(K, 2)        # little-endian: {lo, hi} bits
+        cnt = host[2:2 + 2 * K:2].copy().view(np.uint32).reshape(K, 2)         # {n, n_pos}
+        return IsotonicCalibrator({"lo": ends[:, 0].copy().view(np.float32), "hi": ends[:, 1].copy().view(np.float32),
+                                   "n": cnt[:, 0].astype(np.int64), "n_pos": cnt[:, 1].astype(np.int64)}, device=self.device)
+
+    def isotonic(self, group=None, stage_on_cpu: bool = False) -> IsotonicCalibrator:
+        """The exact isotonic fit of the samples held (they stay; compute() and calibration() are not
+        affected) as an IsotonicCalibrator: pool-adjacent-violators pooling on >=, computed as the lower
+        convex hull of the cumulative (samples, positives) diagram with 64-bit integers (§25).  One sort of
+        the keys, one read; independent of the samples' order, the update sizes and the rank split.
+        Raises the ValueError compute() raises for the same status word, and ValueError with no sample.
+        group / stage_on_cpu: as in compute() (the same all-gather)."""
+        keys, n, rec, _ = self._gather(group, stage_on_cpu)
+        return self._isotonic(keys, n, rec)
 
     # ------------------------------------------------------------------ DeLong (DESIGN.md §23)
     def _place_into(self, keys: torch.Tensor, n: int, rec: torch.Tensor) -> torch.Tensor:

@@ -57,6 +57,11 @@ def _state_of(state) -> Dict[str, torch.Tensor]:
     raise TypeError(f"state must be a state_dict, a FiBiNETTrainer or the model module, not {type(state).__name__}")
 
 
+def _check_calibrator(calibrator, logits: bool) -> None:
+    if calibrator is not None and logits:
+        raise ValueError("a calibrator maps probabilities; it cannot be combined with logits=True")
+
+
 def _check_lists(item_seq, candidates, by: str, target_slot=None, k: Optional[int] = None):
     """The argument checks of the ``*_lists`` methods, before anything is launched: -> (U, C).  Shapes
     only, so it needs no device."""
@@ -298,13 +303,18 @@ class Recommender:
 
     # ------------------------------------------------------------------ public
     @torch.no_grad()
-    def score(self, item_seq: Optional[torch.Tensor], logits: bool = False) -> torch.Tensor:
+    def score(self, item_seq: Optional[torch.Tensor], logits: bool = False, calibrator=None) -> torch.Tensor:
         """Probabilities (or logits) [U, M] of every (user, catalogue item) pair; ``item_seq=None``:
-        one cold user whose history field is zero."""
+        one cold user whose history field is zero.  ``calibrator``: a metrics.IsotonicCalibrator applied
+        to the probabilities in place (one more launch); not with ``logits=True``.  ``topk`` needs none:
+        it ranks on logits and the map is monotone."""
+        _check_calibrator(calibrator, logits)
         with torch.cuda.device(self.device):
             st = _lib.stream_handle(self.device)
             _, hist, U, _ = self._hist(item_seq, st)
             out = self._sweep(hist, U, logits)
+            if calibrator is not None:
+                calibrator.apply(out, out=out)
         return out
 
     def _sweep(self, hist, U: int, logits: bool, cand: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -431,19 +441,23 @@ class Recommender:
 
     @torch.no_grad()
     def score_lists(self, item_seq: Optional[torch.Tensor], candidates: torch.Tensor, *, by: str = "item_id",
-                    logits: bool = False) -> torch.Tensor:
+                    logits: bool = False, calibrator=None) -> torch.Tensor:
         """Probabilities (or logits) [U, C] of every user's own candidate list: ``candidates`` [U, C]
         (int64) holds item ids (``by="item_id"``, mapped by :meth:`positions`) or catalogue positions
         (``by="index"``).  A negative entry, or an id the catalogue lacks, is an empty slot and reads
         probability 0 / logit -inf; a position >= M does too and sets the flag ``check_ids()`` raises
         on.  ``item_seq=None`` with one row of candidates is the cold user.  Only the U x C pairs are
-        scored (chunked along the slots); nothing is copied to the host and nothing synchronises."""
+        scored (chunked along the slots); nothing is copied to the host and nothing synchronises.
+        ``calibrator``: as in :meth:`score`; an empty slot still reads 0."""
+        _check_calibrator(calibrator, logits)
         U, _ = _check_lists(item_seq, candidates, by)
         with torch.cuda.device(self.device):
             st = _lib.stream_handle(self.device)
             pos = self._lists(candidates, by)
             _, hist, U, _ = self._hist(item_seq, st)
             out = self._sweep(hist, U, logits, pos)
+            if calibrator is not None:
+                calibrator.apply(out, out=out)
             live = (pos >= 0) & (pos < self.M)
             out = torch.where(live, out, torch.full_like(out, float("-inf") if logits else 0.0))
         return out

@@ -87,7 +87,10 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
     with ``valid_calibration_bins`` (B in [1, 1024]) also "valid_ece", "valid_pcoc", "valid_ne": [per epoch]
     and `` | Valid ECE: ... | PCOC: ... | NE: ... `` on the epoch line; with ``valid_auc_ci`` (true, or a
     level in (0, 1)) also "valid_auc_se": [per epoch], DeLong's standard error of the validation AUC, and
-    `` | AUC SE: 0.0012`` on the epoch line.
+    `` | AUC SE: 0.0012`` on the epoch line; with ``valid_isotonic: true`` the exact isotonic calibrator of
+    each epoch's validation scores is fitted on the device, `` | iso blocks: K`` is appended
+    to the epoch line, "valid_iso_blocks": [per epoch] is returned, and at each new best AUC the calibrator
+    is saved next to the checkpoint as ``<checkpoint stem>.isotonic.json`` (predict.py --calibrator reads it).
 
     Full-state checkpoints (checkpoint.py; also the model-config keys ``resume_from``,
     ``checkpoint_every_steps``, ``state_dir``): save_every: one every that many optimizer steps and at
@@ -134,7 +137,11 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
     valid_ece, valid_pcoc, valid_ne = [], [], []
     auc_ci = model_cfg.get("valid_auc_ci")                # true or a level: also report DeLong's standard error of the AUC
     valid_auc_se = []
+    fit_iso = bool(model_cfg.get("valid_isotonic"))       # also fit the isotonic calibrator of the validation scores
+    valid_iso_blocks = []
     ev_args = {}
+    if fit_iso:
+        ev_args["fit_isotonic"] = True
     if auc_ci:
         ev_args["auc_ci"] = auc_ci
     if group_by:
@@ -150,6 +157,8 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
         state_dir = resume or os.path.join("..", "checkpoints", "state")
     lists = {"valid_logloss": valid_logloss, "valid_gauc": valid_gauc, "valid_ece": valid_ece,
              "valid_pcoc": valid_pcoc, "valid_ne": valid_ne, "valid_auc_se": valid_auc_se}
+    if fit_iso:
+        lists["valid_iso_blocks"] = valid_iso_blocks
 
     def save_state(epoch: int, steps: int, loss_sum: float) -> None:
         """The run as it stands: `steps` steps of (0-based) `epoch` done, their losses summing to loss_sum."""
@@ -238,6 +247,10 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
             se = float(ev["auc_se"]) if len(valid_loader) else None
             valid_auc_se.append(se)
             line += f" | AUC SE: {se if se is None else f'{se:.4f}'}"
+        iso = ev.get("calibrator") if fit_iso else None
+        if fit_iso:
+            valid_iso_blocks.append(None if iso is None else len(iso))
+            line += f" | iso blocks: {None if iso is None else len(iso)}"
         log0(line)
         if auc is not None and auc > best_auc:
             best_auc = auc
@@ -246,6 +259,8 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
                 os.makedirs(os.path.dirname(os.path.abspath(ckpt)), exist_ok=True)
                 torch.save(sd, ckpt)
                 log0(f"New best FiBiNET AUC; saved to {ckpt}")
+                if iso is not None:
+                    iso.save(os.path.splitext(ckpt)[0] + ".isotonic.json")
         if saving:
             save_state(epoch + 1, 0, 0.0)
         if stopped:
@@ -262,6 +277,8 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
         out.update(valid_ece=valid_ece, valid_pcoc=valid_pcoc, valid_ne=valid_ne)
     if auc_ci:
         out["valid_auc_se"] = valid_auc_se
+    if fit_iso:
+        out["valid_iso_blocks"] = valid_iso_blocks
     return out
 
 

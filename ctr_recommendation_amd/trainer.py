@@ -1202,10 +1202,14 @@ class FiBiNETTrainer:
                 dist.broadcast(t, src=0, group=self.group)
 
     @torch.no_grad()
-    def predict(self, batch: Dict[str, torch.Tensor], logits: bool = False) -> torch.Tensor:
+    def predict(self, batch: Dict[str, torch.Tensor], logits: bool = False, calibrator=None) -> torch.Tensor:
         """Eval-mode probabilities (or logits) of this rank's batch.  N > 1: collective (the row
         exchange, and rank 0's BatchNorm statistics when sync_bn is off); a rank with an empty slice
-        (a last batch smaller than the world) still joins them and returns an empty tensor."""
+        (a last batch smaller than the world) still joins them and returns an empty tensor.
+        calibrator: a metrics.IsotonicCalibrator applied to the probabilities on the device (one more
+        launch); not with logits=True."""
+        if calibrator is not None and logits:
+            raise ValueError("predict: a calibrator maps probabilities; it cannot be combined with logits=True")
         self.flush()
         self._bn_from_rank0()
         cfg = ops.FwdConfig(**{**self.fcfg.__dict__, "training": False})
@@ -1219,11 +1223,14 @@ class FiBiNETTrainer:
         if B == 0:
             return torch.empty(0, dtype=torch.float32, device=self.device)
         a = ops.forward(self.p, batch, cfg, None, table_rows=rows, pos=pos, err=self.err)
+        if calibrator is not None:
+            return calibrator.apply(a["probs"])
         return (a["logits"] if logits else a["probs"]).clone()
 
     @torch.no_grad()
     def evaluate(self, loader_or_batches, metrics=None, group_by: Optional[str] = None,
-                 calibration_bins: Optional[int] = None, auc_ci=None) -> Dict:
+                 calibration_bins: Optional[int] = None, auc_ci=None, fit_isotonic: bool = False,
+                 calibrator=None) -> Dict:
         """Validation metrics of (batch, labels) pairs without a per-batch host transfer: predict()'s
         eval-mode forward per batch, its probabilities packed straight into a metrics.DeviceMetrics
         (one launch per batch), then one exact device reduce and one 40-byte read.  Returns
@@ -1241,8 +1248,14 @@ class FiBiNETTrainer:
         gathered once for every reduce asked at N > 1.
         auc_ci: a level in (0, 1), or True for 0.95: the result also holds {"auc_se", "auc_ci_lo",
         "auc_ci_hi", "auc_ci_level"}, DeLong's standard error and interval of the AUC
-        (DeviceMetrics.auc_ci(); NaN with fewer than 2 samples of a class)."""
+        (DeviceMetrics.auc_ci(); NaN with fewer than 2 samples of a class).
+        fit_isotonic: the result also holds "calibrator", the metrics.IsotonicCalibrator fitted exactly on
+        these samples' raw scores, over the keys already gathered (DeviceMetrics.isotonic()); None when there was no sample.
+        calibrator: an IsotonicCalibrator applied to every batch's probabilities before they are packed,
+        so every number returned is of the corrected scores; not together with fit_isotonic."""
         from .metrics import DeviceMetrics, _check_level, normalized_entropy
+        if fit_isotonic and calibrator is not None:
+            raise ValueError("evaluate: fit_isotonic fits on the raw scores; it cannot be combined with calibrator=")
         grouped = group_by is not None
         if auc_ci is not None:
             auc_ci = _check_level(0.95 if auc_ci is True else auc_ci)
@@ -1262,7 +1275,7 @@ class FiBiNETTrainer:
         metrics.reset()
         for batch, labels in loader_or_batches:
             ids = batch[group_by] if grouped else None
-            probs = self.predict(batch)
+            probs = self.predict(batch, calibrator=calibrator)
             if probs.numel():
                 metrics.update(probs, labels, group_ids=ids)
         group = None
@@ -1278,6 +1291,8 @@ class FiBiNETTrainer:
         if auc_ci is not None:
             ci = metrics._auc_ci(keys, n, rec, auc_ci)
             out.update(auc_se=ci["auc_se"], auc_ci_lo=ci["ci_lo"], auc_ci_hi=ci["ci_hi"], auc_ci_level=ci["level"])
+        if fit_isotonic:
+            out["calibrator"] = metrics._isotonic(keys, n, rec) if n else None      # nothing to fit on
         return out
 
     def check_ids(self) -> None:

@@ -773,6 +773,40 @@ size_t fbn_calib_workspace_size(long long n);
 int fbn_calib_reduce(const uint32_t* keys, long long n, int bins, void* ws, size_t ws_bytes, uint64_t* out,
                      unsigned* status, void* stream);
 
+/* ---------------------------------------------------------------- device metrics: isotonic calibrator
+ * The calibration table says whether the probabilities are right; this makes them right.  The reference
+ * has no calibrator: a user fits sklearn's isotonic regression on the host from every batch's
+ * probabilities (src/train_fibinet.py:133-146).  Over 0/1 labels the fit is an integer problem over the
+ * keys fbn_eval_pack wrote: sort the keys; a group is a run of equal score bits;
+ * P_0 = (0, 0), P_g = (samples, positives of groups 1 .. g); the blocks are the edges of the lower convex
+ * hull of P_0 .. P_G with collinear points dropped (b between hull neighbours a < b < c goes iff
+ * (S_b - S_a)(N_c - N_b) >= (S_c - S_b)(N_b - N_a), 64-bit integers).  Block values pos / n increase
+ * strictly; the result does not depend on the samples' order.  K <= fbn_isotonic_max_blocks(n) =
+ * floor((3n)^(2/3) / 2) + 2 (host-only query).
+ * fbn_isotonic_fit over keys[0 .. n), 0 <= n < 2^31: table (uint64, 8-B aligned, table_words >=
+ * 2 * fbn_isotonic_max_blocks(n) + 2):
+ *     word 0            K
+ *     word 1 + 2j       bits(lo_j) | bits(hi_j) << 32: the scores of block j's first and last group
+ *     word 2 + 2j       n_j | pos_j << 32
+ *     word 1 + 2K       the value of *status after this fit (one copy reads everything)
+ *   n == 0 writes K = 0 (and the status word).  keys is not modified; a key above (0x3F800000 << 1) | 1 is
+ *   counted as 1.0 and sets bit 3 of *status.  ws: >= fbn_isotonic_workspace_size(n) bytes (host-only
+ *   query), 16-B aligned.  A null pointer, n < 0 or n >= 2^31, a short table and a small or misaligned ws
+ *   return FBN_ERR_ARG before any device work.  The number and sizes of the launches depend on n alone;
+ *   no float operation, no atomics except the status bit, no host sync, no allocation.
+ * fbn_isotonic_apply: out[i] = the calibrated p[i], i < n (out may be p); K is read from table[0] on the
+ * device (K = 0 gives NaN).  With v_j = (double)pos_j / (double)n_j, x = (double)p and j the first block
+ * with hi_j >= x: none: v_{K-1}; x >= lo_j or j == 0: v_j; else (mode 0, "interp")
+ * min(v_{j-1} + (x - hi_{j-1}) / (lo_j - hi_{j-1}) * (v_j - v_{j-1}), v_j), every float64 operation
+ * rounded on its own, the result rounded once to fp32; mode 1 ("step") returns v_j without interpolating.
+ * NaN passes through; nothing is flagged.  A null pointer, an unknown mode and n outside [0, 2^31) return
+ * FBN_ERR_ARG before any device work. */
+size_t fbn_isotonic_workspace_size(long long n);
+long long fbn_isotonic_max_blocks(long long n);
+int fbn_isotonic_fit(const uint32_t* keys, long long n, void* ws, size_t ws_bytes, uint64_t* table, long long table_words,
+                     unsigned* status, void* stream);
+int fbn_isotonic_apply(const float* p, long long n, const uint64_t* table, int mode, float* out, void* stream);
+
 /* ---------------------------------------------------------------- device metrics: DeLong placements and sums
  * The reference reports one AUC per epoch (roc_auc_score, src/utils.py:18-27) and nothing about its
  * noise: how much of a difference between two checkpoints is chance, a user has to work out on the host
