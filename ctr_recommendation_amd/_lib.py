@@ -82,6 +82,8 @@ SIGNATURES = {
     "fbn_bn_act_fwd": (I, [P, P, I, I, P, P, P, P, F, P, U, P, P, P, P]),
     "fbn_bn_act_fwd_img": (I, [P, P, I, I, P, P, P, P, F, P, U, P, P, P, P]),
     "fbn_bn_act_head_fwd": (I, [P, P, I, I, P, P, P, P, F, P, U, P, P, P, P, P, P, P, P, P, F, P, F, P]),
+    "fbn_bn_act_head_fwd_w": (I, [P, P, I, I, P, P, P, P, F, P, U, P, P, P, P, P, P, P, P, P, F, P, F, P, F, F, P,
+                                  P]),
     "fbn_bn_bwd_reduce": (I, [P, P, P, P, F, P, P, I, I, P, P, P]),
     "fbn_bn_bwd_apply": (I, [P, P, P, P, F, P, P, P, P, I, I, P, D, P, P, P, P, P, P, P]),
     "fbn_convert_bf16": (I, [P, I, P]),
@@ -89,6 +91,7 @@ SIGNATURES = {
     "fbn_colsum_workspace_size": (SZ, [I, I]),
     "fbn_colsum": (I, [P, I, I, I, P, F, P, P]),
     "fbn_head_fwd": (I, [P, P, P, I, I, P, P, P, P, P, F, P]),
+    "fbn_head_fwd_w": (I, [P, P, P, I, I, P, P, P, P, P, F, P, F, F, P, P]),
     "fbn_sigmoid_bwd": (I, [P, P, P, I, P]),
     "fbn_outer": (I, [P, P, P, I, I, P]),
     "fbn_sum": (I, [P, I, P, F, P]),
@@ -144,6 +147,7 @@ SIGNATURES = {
                                     I, LL, P, I, I, P]),
     "fbn_collate": (I, [P, I, P, P, I, I, P, P, P, P, P, LL, P, P, I, P, P, P, P, P, P, P, P, P]),
     "fbn_collate_zero_if": (I, [P, LL, P, P]),
+    "fbn_collate_f32": (I, [P, I, P, LL, P, P]),
     "fbn_eval_pack": (I, [P, P, LL, P, P, P]),
     "fbn_eval_workspace_size": (SZ, [LL]),
     "fbn_eval_reduce": (I, [P, LL, P, SZ, P, P, P]),
@@ -203,6 +207,7 @@ SIGNATURES = {
     "fbn_comm_watchdog_fired": (I, [P]),
 }
 
+FBN_ERR_BIT_WEIGHT = 4        # include/fibinet.h: sticky *err bit of a NaN, infinite or negative sample weight
 FBN_SORT_TILE = 2048          # include/fibinet.h: keys per workgroup of fbn_sort_u64's passes
 FBN_GAUC_REC_WORDS = 8        # include/fibinet.h: 8-byte words of fbn_gauc_reduce's record
 FBN_CALIB_MAX_BINS = 1024     # include/fibinet.h: bins of fbn_calib_reduce at most
@@ -458,6 +463,7 @@ class StepProgram:
         self.h = h.value
         self.device = torch.device(device if device is not None else "cuda")
         self.keep = []
+        self.names = []                # the recorded calls' entry points, in order
         self._slots = {}
         self._nslot = 0
         self.pool = None
@@ -479,6 +485,7 @@ class StepProgram:
         ia = (ctypes.c_ulonglong * max(1, len(ints)))(*ints)
         fa = (ctypes.c_double * max(1, len(flts)))(*flts)
         call_raw("fbn_plan_add_call", self.h, name.encode(), ia, len(ints), fa, len(flts))
+        self.names.append(name)
 
     def slot_of(self, ev) -> int:
         k = id(ev)

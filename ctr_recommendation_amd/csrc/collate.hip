@@ -114,6 +114,24 @@ extern "C" int fbn_collate(const int64_t* perm, int B, const int64_t* item, cons
   return FBN_OK;
 }
 
+// one more f32 column (the sample weights) at the batch's rows
+__global__ void collate_f32_kernel(const int64_t* __restrict__ rows, int B, const float* __restrict__ src,
+                                   long long n, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B) return;
+  const long long r = rows[i];
+  out[i] = (r >= 0 && r < n) ? src[r] : __builtin_nanf("");
+}
+
+extern "C" int fbn_collate_f32(const int64_t* rows, int B, const float* src, long long n, float* out,
+                               void* stream) {
+  if (B <= 0) return FBN_OK;
+  if (!rows || !src || !out || n < 0) { fbn_set_error("fbn_collate_f32: rows, src, out and n >= 0 are required"); return FBN_ERR_ARG; }
+  fbn_launch(collate_f32_kernel, dim3(fbn_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, rows, B, src, n, out);
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}
+
 extern "C" int fbn_collate_zero_if(float* x, long long n, const int* flag, void* stream) {
   if (n <= 0) return FBN_OK;
   if (!x || !flag) { fbn_set_error("fbn_collate_zero_if: x and flag are required"); return FBN_ERR_ARG; }

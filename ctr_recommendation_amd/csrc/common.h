@@ -33,6 +33,9 @@ enum {
   FBN_ERR_LAUNCH = 2,
   FBN_ERR_UNSUPPORTED = 3,
 };
+// Bits of the sticky *err word (include/fibinet.h): 1 = an id outside its table, 2 = a step past
+// total_steps, 4 = a sample weight that is NaN, infinite or negative
+#define FBN_ERR_BIT_WEIGHT 4
 
 // round-to-nearest-even f32 -> bf16 (NaN-safe through the hardware cvt at -O3)
 __device__ __forceinline__ short f2bf(float x) {

@@ -294,10 +294,18 @@ struct HeadArgs {
   const float* w; const float* bias;
   float* logits; float* probs; const float* labels; float* loss_terms; float* gout;
   float denom;
+  // the weighted loss (fbn_head_fwd_w / fbn_bn_act_head_fwd_w; weighted = 0: plain mean BCE, none read)
+  int weighted;
+  const float* sample_w;   // [B] or null (w = 1)
+  float pos_weight, smooth;
+  int* err;                // sticky flags: FBN_ERR_BIT_WEIGHT on a NaN, infinite or negative weight
 };
 // Linear(C,1) + sigmoid + BCE terms + dL/dlogit of one row from the wave's lane partials
 // (lane q holds columns 4q..4q+3): shared by head_fwd_kernel and the fused BN2 + head kernel
-// The row's outputs from its summed dot product s (one lane)
+// The row's outputs from its summed dot product s (one lane).
+// Weighted (include/fibinet.h, fbn_head_fwd_w): t~ = t (1 - eps) + eps / 2, the positive term scaled by
+// pos_weight, the term and the gradient by the sample's weight; the numerator (1 - t~) p - pi t~ (1 - p)
+// is p - t bit for bit at pi = 1, eps = 0, t in {0, 1}, so neutral options give the plain form's bits.
 __device__ __forceinline__ float head_lane(float s, int row, const HeadArgs& h) {
   float go = 0.f;
   const float o = s + h.bias[0];
@@ -307,11 +315,29 @@ __device__ __forceinline__ float head_lane(float s, int row, const HeadArgs& h) 
   if (h.labels) {
     const float t = h.labels[row];
     const float lp = fmaxf(logf(pr), -100.f), l1p = fmaxf(logf(1.f - pr), -100.f);
-    if (h.loss_terms) h.loss_terms[row] = -(t * lp + (1.f - t) * l1p);
-    if (h.gout) {
-      const float gp = ((pr - t) / fmaxf((1.f - pr) * pr, 1e-12f)) / h.denom;
-      go = gp * (1.f - pr) * pr;
-      h.gout[row] = go;
+    if (!h.weighted) {
+      if (h.loss_terms) h.loss_terms[row] = -(t * lp + (1.f - t) * l1p);
+      if (h.gout) {
+        const float gp = ((pr - t) / fmaxf((1.f - pr) * pr, 1e-12f)) / h.denom;
+        go = gp * (1.f - pr) * pr;
+        h.gout[row] = go;
+      }
+    } else {
+      float wt = h.sample_w ? h.sample_w[row] : 1.f;
+      const bool bad = !(wt >= 0.f && wt <= 3.402823466e38f);   // NaN, negative, +inf
+      if (bad) {
+        if (h.err) atomicOr(h.err, FBN_ERR_BIT_WEIGHT);
+        wt = 0.f;
+      }
+      const float ts = t * (1.f - h.smooth) + h.smooth / 2.f;
+      const float a = h.pos_weight * ts, b = 1.f - ts;
+      if (h.loss_terms) h.loss_terms[row] = bad ? 0.f : wt * -(a * lp + b * l1p);
+      if (h.gout) {
+        const float num = b * pr - a * (1.f - pr);
+        const float gp = (wt * num / fmaxf((1.f - pr) * pr, 1e-12f)) / h.denom;
+        go = bad ? 0.f : gp * (1.f - pr) * pr;
+        h.gout[row] = go;
+      }
     }
   }
   return go;
@@ -1118,20 +1144,17 @@ __global__ void __launch_bounds__(256) sum_jobs_sq_kernel(SumJobs J, SumSq Q) {
 // ------------------------------------------------------------------ head: o = h.w + b, p = sigmoid(o), BCE
 // one wave per row.  gout[b] = dL/do when labels are given (mean BCE over `denom` samples),
 // using ATen's BCE backward ((p-t)/max((1-p)p, 1e-12)/N) followed by sigmoid backward (g(1-p)p).
-__global__ void head_fwd_kernel(const float* __restrict__ H, const float* __restrict__ w, const float* __restrict__ bias,
-                                int B, int C, float* __restrict__ logits, float* __restrict__ probs,
-                                const float* __restrict__ labels, float* __restrict__ loss_terms,
-                                float* __restrict__ gout, float denom) {
+__global__ void head_fwd_kernel(const float* __restrict__ H, int B, int C, HeadArgs head) {
   const int lane = threadIdx.x & 63;
   const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (row >= B) return;
   float s = 0.f;
   for (int c = lane * 4; c < C; c += 256) {
     const f32x4 h = *reinterpret_cast<const f32x4*>(H + (size_t)row * C + c);
-    const f32x4 ww = *reinterpret_cast<const f32x4*>(w + c);
+    const f32x4 ww = *reinterpret_cast<const f32x4*>(head.w + c);
     s += h[0] * ww[0] + h[1] * ww[1] + h[2] * ww[2] + h[3] * ww[3];
   }
-  head_row(s, row, lane, HeadArgs{w, bias, logits, probs, labels, loss_terms, gout, denom});
+  head_row(s, row, lane, head);
 }
 
 // sigmoid backward only (drop-in mode: torch computes BCE and hands us dL/dp)
@@ -1358,34 +1381,71 @@ extern "C" int fbn_bn_act_fwd_img(const float* X, float* Y, int B, int C, const 
   return FBN_OK;
 }
 
-// BN + ReLU + dropout of the last hidden layer (C = 256) fused with the head (fbn_head_fwd's outputs)
-extern "C" int fbn_bn_act_head_fwd(const float* X, float* Y, int B, int C, const float* mean, const float* invstd,
-                                   const float* g, const float* b, float p_drop, const unsigned long long* rng,
-                                   unsigned stream_id, unsigned char* mask_out, const unsigned char* mask_in,
-                                   const float* hw, const float* hbias, float* logits, float* probs,
-                                   const float* labels, float* loss_terms, float* gout, float denom,
-                                   double* bwd_part, float bwd_scale, void* stream) {
+// The weighted loss's scalars, checked on the host before any launch
+static int head_loss_opts_ok(float pos_weight, float label_smoothing) {
+  if (!(pos_weight > 0.f && pos_weight <= 3.402823466e38f)) {
+    fbn_set_error("head: pos_weight must be finite and > 0");
+    return 0;
+  }
+  if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) {
+    fbn_set_error("head: label_smoothing must lie in [0, 1)");
+    return 0;
+  }
+  return 1;
+}
+
+// BN + ReLU + dropout of the last hidden layer (C = 256) fused with the head: both entry points
+static int bn_act_head_launch(const float* X, float* Y, int B, int C, const float* mean, const float* invstd,
+                              const float* g, const float* b, float p_drop, const unsigned long long* rng,
+                              unsigned stream_id, unsigned char* mask_out, const unsigned char* mask_in,
+                              const HeadArgs& head, double* bwd_part, float bwd_scale, void* stream) {
   if (B <= 0) return FBN_OK;
   if (C != 256) { fbn_set_error("bn_act_head: the fused head needs C == 256"); return FBN_ERR_UNSUPPORTED; }
   if (p_drop > 0.f && !rng && !mask_in) { fbn_set_error("bn_act: dropout needs an rng state or a mask"); return FBN_ERR_ARG; }
-  if (bwd_part && !gout) { fbn_set_error("bn_act_head: backward partials need labels / gout"); return FBN_ERR_ARG; }
+  if (bwd_part && !head.gout) { fbn_set_error("bn_act_head: backward partials need labels / gout"); return FBN_ERR_ARG; }
   if (bwd_part) {
     // the row chunks of fbn_bn_bwd_fused, so its reduce reads these partials as its own: all nch of
     // them are launched (as bn_bwd_partial4's grid) -- past B = 8192 nch is capped, rpc is rounded up
     // and the last chunks hold no rows; they skip the row loop and store zeros for the reduce to add
     const int nch = bn_bwd_chunks(B, C), rpc = (B + nch - 1) / nch;
     fbn_launch(bn_act_head_bwd4_kernel, dim3(1, nch), dim3(256), 0, (hipStream_t)stream, X, Y, B,
-               C, rpc, mean, invstd, g, b, p_drop, rng, stream_id, mask_out, mask_in,
-               HeadArgs{hw, hbias, logits, probs, labels, loss_terms, gout, denom}, bwd_part, bwd_scale);
+               C, rpc, mean, invstd, g, b, p_drop, rng, stream_id, mask_out, mask_in, head, bwd_part, bwd_scale);
     FBN_CHECK_LAUNCH();
     return FBN_OK;
   }
   const int rpc = FBN_BN_ACT_ROWS;
   fbn_launch(bn_act_fwd2_kernel<true>, dim3(1, fbn_cdiv(B, rpc)), dim3(256), 0, (hipStream_t)stream, X, Y, B,
                      C, rpc, mean, invstd, g, b, p_drop, rng, stream_id, mask_out, mask_in, (short*)nullptr,
-                     HeadArgs{hw, hbias, logits, probs, labels, loss_terms, gout, denom}, 0LL);
+                     head, 0LL);
   FBN_CHECK_LAUNCH();
   return FBN_OK;
+}
+
+// (fbn_head_fwd's outputs)
+extern "C" int fbn_bn_act_head_fwd(const float* X, float* Y, int B, int C, const float* mean, const float* invstd,
+                                   const float* g, const float* b, float p_drop, const unsigned long long* rng,
+                                   unsigned stream_id, unsigned char* mask_out, const unsigned char* mask_in,
+                                   const float* hw, const float* hbias, float* logits, float* probs,
+                                   const float* labels, float* loss_terms, float* gout, float denom,
+                                   double* bwd_part, float bwd_scale, void* stream) {
+  return bn_act_head_launch(X, Y, B, C, mean, invstd, g, b, p_drop, rng, stream_id, mask_out, mask_in,
+                            HeadArgs{hw, hbias, logits, probs, labels, loss_terms, gout, denom}, bwd_part, bwd_scale,
+                            stream);
+}
+
+// ... with the weighted loss (fbn_head_fwd_w's outputs; bwd_part from the weighted gout)
+extern "C" int fbn_bn_act_head_fwd_w(const float* X, float* Y, int B, int C, const float* mean, const float* invstd,
+                                     const float* g, const float* b, float p_drop, const unsigned long long* rng,
+                                     unsigned stream_id, unsigned char* mask_out, const unsigned char* mask_in,
+                                     const float* hw, const float* hbias, float* logits, float* probs,
+                                     const float* labels, float* loss_terms, float* gout, float denom,
+                                     double* bwd_part, float bwd_scale, const float* sample_w, float pos_weight,
+                                     float label_smoothing, int* err, void* stream) {
+  if (!head_loss_opts_ok(pos_weight, label_smoothing)) return FBN_ERR_ARG;
+  return bn_act_head_launch(X, Y, B, C, mean, invstd, g, b, p_drop, rng, stream_id, mask_out, mask_in,
+                            HeadArgs{hw, hbias, logits, probs, labels, loss_terms, gout, denom, 1, sample_w,
+                                     pos_weight, label_smoothing, err},
+                            bwd_part, bwd_scale, stream);
 }
 
 // BN(+ReLU+dropout) backward, stage 1: local sums red_d[3][C] = {sum dy, sum (x-mean) dy, sum gvec*hact}.
@@ -1449,15 +1509,29 @@ extern "C" int fbn_colsum(const float* X, int B, int C, int ldx, float* out, flo
   return FBN_OK;
 }
 
+static int head_launch(const float* H, int B, int C, const HeadArgs& head, void* stream) {
+  if (B <= 0) return FBN_OK;
+  if (C & 3) { fbn_set_error("head: C % 4"); return FBN_ERR_ARG; }
+  fbn_launch(head_fwd_kernel, dim3(fbn_cdiv((long long)B * 64, 256)), dim3(256), 0, (hipStream_t)stream, H, B, C,
+             head);
+  FBN_CHECK_LAUNCH();
+  return FBN_OK;
+}
+
 extern "C" int fbn_head_fwd(const float* H, const float* w, const float* bias, int B, int C, float* logits,
                             float* probs, const float* labels, float* loss_terms, float* gout, float denom,
                             void* stream) {
-  if (B <= 0) return FBN_OK;
-  if (C & 3) { fbn_set_error("head: C % 4"); return FBN_ERR_ARG; }
-  fbn_launch(head_fwd_kernel, dim3(fbn_cdiv((long long)B * 64, 256)), dim3(256), 0, (hipStream_t)stream, H, w,
-                     bias, B, C, logits, probs, labels, loss_terms, gout, denom);
-  FBN_CHECK_LAUNCH();
-  return FBN_OK;
+  return head_launch(H, B, C, HeadArgs{w, bias, logits, probs, labels, loss_terms, gout, denom}, stream);
+}
+
+extern "C" int fbn_head_fwd_w(const float* H, const float* w, const float* bias, int B, int C, float* logits,
+                              float* probs, const float* labels, float* loss_terms, float* gout, float denom,
+                              const float* sample_w, float pos_weight, float label_smoothing, int* err,
+                              void* stream) {
+  if (!head_loss_opts_ok(pos_weight, label_smoothing)) return FBN_ERR_ARG;
+  return head_launch(H, B, C, HeadArgs{w, bias, logits, probs, labels, loss_terms, gout, denom, 1, sample_w,
+                                       pos_weight, label_smoothing, err},
+                     stream);
 }
 
 extern "C" int fbn_sigmoid_bwd(const float* gp, const float* probs, float* gout, int B, void* stream) {

@@ -112,9 +112,12 @@ class ItemInfoTable:
 class ColumnarDataset:
     """A parquet split held column-wise in HBM (the role of ParquetDataset, src/dataloader.py:10-48).
 
-    ``item_seq`` keeps its stored width Ls; collation keeps its last ``max_len`` columns."""
+    ``item_seq`` keeps its stored width Ls; collation keeps its last ``max_len`` columns.
+    weight_col: a column of per-sample loss weights kept as f32 (a train loader then yields it as
+    ``batch["sample_weight"]``, which FiBiNETTrainer.step applies; validation metrics stay unweighted)."""
 
-    def __init__(self, cols: Dict[str, np.ndarray], device, label_col: str = "label"):
+    def __init__(self, cols: Dict[str, np.ndarray], device, label_col: str = "label",
+                 weight_col: Optional[str] = None):
         self.device = torch.device(device)
         n = len(cols["item_id"])
         self.n = n
@@ -134,12 +137,21 @@ class ColumnarDataset:
         if self.has_label:
             self.cols["label"] = torch.from_numpy(np.array(cols[label_col], dtype=np.float32, order="C")).to(
                 self.device)
+        self.weight_col = weight_col
+        if weight_col is not None:
+            if weight_col not in cols:
+                raise KeyError(f"weight_col {weight_col!r} is not a column of the dataset")
+            w = np.asarray(cols[weight_col])
+            if w.ndim != 1 or len(w) != n:
+                raise ValueError(f"column {weight_col!r}: expected {n} scalars, got shape {w.shape}")
+            self.cols["sample_weight"] = torch.from_numpy(np.array(w, dtype=np.float32, order="C")).to(self.device)
 
     @classmethod
-    def from_parquet(cls, path: str, device, label_col: str = "label") -> "ColumnarDataset":
+    def from_parquet(cls, path: str, device, label_col: str = "label",
+                     weight_col: Optional[str] = None) -> "ColumnarDataset":
         if not path.endswith(".parquet") and not path.endswith(".pq"):
             path += ".parquet"                       # MMCTRDataLoader appends it (src/dataloader.py:130-131)
-        return cls(read_parquet_columns(path), device, label_col)
+        return cls(read_parquet_columns(path), device, label_col, weight_col)
 
     def __len__(self) -> int:
         return self.n
@@ -212,7 +224,8 @@ class DeviceLoader:
         return torch.arange(n, device=self.device)
 
     def collate(self, rows: torch.Tensor, flag: Optional[torch.Tensor] = None):
-        """The batch of dataset rows `rows` (int64 device tensor): one fbn_collate launch."""
+        """The batch of dataset rows `rows` (int64 device tensor): one fbn_collate launch (train mode
+        over a dataset with a weight column: and one fbn_collate_f32 for ``sample_weight``)."""
         _lib.require_hip(rows, "row index")
         B = rows.shape[0]
         dev = self.device
@@ -238,6 +251,11 @@ class DeviceLoader:
              info.dim if info else 0, ptr(out["item_id"]), ptr(out.get("item_seq")), ptr(out.get("likes_level")),
              ptr(out.get("views_level")), ptr(out.get("user_id")), ptr(lab), ptr(out.get("item_emb_d128")),
              ptr(flag), _lib.stream_handle(dev))
+        sw = c.get("sample_weight")
+        if sw is not None and lab is not None:
+            out["sample_weight"] = torch.empty(B, dtype=torch.float32, device=dev)
+            call("fbn_collate_f32", ptr(rows), B, ptr(sw), sw.shape[0], ptr(out["sample_weight"]),
+                 _lib.stream_handle(dev))
         return out, lab
 
     def __iter__(self) -> Iterator:
@@ -290,11 +308,14 @@ class DeviceLoader:
 
 def make_loaders(dataset_cfg: Dict, model_cfg: Dict, device, rank: int = 0, world: int = 1,
                  seed: int = 2025) -> Tuple[DeviceLoader, DeviceLoader, ItemInfoTable]:
-    """train / valid loaders from the reference config surface (src/train_fibinet.py:40-61)."""
+    """train / valid loaders from the reference config surface (src/train_fibinet.py:40-61).
+    dataset_cfg["weight_col"] (optional): the train split's per-sample loss weights (validation stays
+    unweighted)."""
     bs = int(model_cfg.get("batch_size", 4096))
     max_len = int(model_cfg.get("max_len", 20))
     info = ItemInfoTable.from_parquet(dataset_cfg["item_info"], device)
-    tr = DeviceLoader(ColumnarDataset.from_parquet(dataset_cfg["train_data"], device), info, bs, shuffle=True,
+    tr = DeviceLoader(ColumnarDataset.from_parquet(dataset_cfg["train_data"], device,
+                                                   weight_col=dataset_cfg.get("weight_col")), info, bs, shuffle=True,
                       max_len=max_len, seed=seed, rank=rank, world=world)
     va = DeviceLoader(ColumnarDataset.from_parquet(dataset_cfg["valid_data"], device), info, bs, shuffle=False,
                       max_len=max_len, seed=seed, rank=rank, world=world)

@@ -521,13 +521,18 @@ def forward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], cfg: Fwd
             masks_out: Optional[Dict[str, torch.Tensor]] = None, acts: Optional[Dict[str, torch.Tensor]] = None,
             probe: Optional[Dict[str, list]] = None, masks_in: Optional[Dict[str, torch.Tensor]] = None,
             after_gather=None, count_batches: bool = True, w16_ready: bool = False,
-            fields: Optional[FieldsStage] = None) -> Dict[str, torch.Tensor]:
+            fields: Optional[FieldsStage] = None, pos_weight: float = 1.0,
+            label_smoothing: float = 0.0) -> Dict[str, torch.Tensor]:
     """Run the forward; returns the activation dict (probs, logits and what backward needs).
 
     p: parameter tensors keyed like the reference state_dict (fp32, contiguous, on device).
     table_rows/pos: multi-GPU mode (rows already exchanged); otherwise p['item_emb.weight'] is read.
     sparse: {'map','slot_row'} to register touched rows for the native sparse-grad Adam.
     labels: if given, fuses BCE: acts['loss_terms'] and acts['gout'] (= dL/dlogit).
+    pos_weight, label_smoothing, batch['sample_weight'] (f32 [B], optional): the weighted loss of
+    fbn_bn_act_head_fwd_w (include/fibinet.h) -- taken only when a scalar is not neutral or the key is
+    present, so an unweighted forward issues exactly the calls it always did; a bad weight sets
+    FBN_ERR_BIT_WEIGHT in err.
     fields: a FieldsStage that replaces the field stage (batch is not read; eval mode only); every
     launch from the bilinear on is the one this function issues for a batch of fields.rows rows.
     """
@@ -750,10 +755,20 @@ def forward(p: Dict[str, torch.Tensor], batch: Dict[str, torch.Tensor], cfg: Fwd
         bpart = buf("bn2_bwd_part", (_lib.lib().fbn_bn_bwd_chunks(B, H2) * 3 * H2,), torch.float64)
     a["bn2_bwd_part"] = bpart
     bscale = 1.0 / (1.0 - cfg.p_drop) if (cfg.training and cfg.p_drop > 0) else 1.0   # = backward()'s scale
-    call("fbn_bn_act_head_fwd", ptr(h2pre), ptr(h2), B, H2, ptr(mean2), ptr(inv2), ptr(p["mlp.5.weight"]),
-         ptr(p["mlp.5.bias"]), float(p_drop), ptr(rng), 2, ptr(m2), ptr(mi2), ptr(p["mlp.8.weight"]),
-         ptr(p["mlp.8.bias"]), ptr(logits), ptr(probs), ptr(labels), ptr(lt), ptr(go),
-         float(loss_denom if loss_denom is not None else ntot), ptr(bpart), float(bscale), st)
+    head = (ptr(h2pre), ptr(h2), B, H2, ptr(mean2), ptr(inv2), ptr(p["mlp.5.weight"]),
+            ptr(p["mlp.5.bias"]), float(p_drop), ptr(rng), 2, ptr(m2), ptr(mi2), ptr(p["mlp.8.weight"]),
+            ptr(p["mlp.8.bias"]), ptr(logits), ptr(probs), ptr(labels), ptr(lt), ptr(go),
+            float(loss_denom if loss_denom is not None else ntot), ptr(bpart), float(bscale))
+    sw = batch.get("sample_weight") if labels is not None else None
+    if labels is not None and (sw is not None or float(pos_weight) != 1.0 or float(label_smoothing) != 0.0):
+        if sw is not None:
+            _lib.require_hip(sw, "sample_weight")
+            if sw.dtype != torch.float32 or tuple(sw.shape) != (B,) or not sw.is_contiguous():
+                raise ValueError(f"batch['sample_weight'] must be a contiguous float32 [{B}] tensor, not "
+                                 f"{sw.dtype} {tuple(sw.shape)}")
+        call("fbn_bn_act_head_fwd_w", *head, ptr(sw), float(pos_weight), float(label_smoothing), ptr(err), st)
+    else:
+        call("fbn_bn_act_head_fwd", *head, st)
     if cfg.training and count_batches and "mlp.1.num_batches_tracked" in p:
         p["mlp.1.num_batches_tracked"].add_(1)
         p["mlp.5.num_batches_tracked"].add_(1)

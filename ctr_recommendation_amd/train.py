@@ -92,6 +92,10 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
     to the epoch line, "valid_iso_blocks": [per epoch] is returned, and at each new best AUC the calibrator
     is saved next to the checkpoint as ``<checkpoint stem>.isotonic.json`` (predict.py --calibrator reads it).
 
+    Weighted training loss: the model-config keys ``loss_pos_weight`` and
+    ``loss_label_smoothing`` and the dataset-config key ``weight_col`` (a train-split column of per-sample
+    weights) reach FiBiNETTrainer; validation and the epoch line stay unweighted.
+
     Full-state checkpoints (checkpoint.py; also the model-config keys ``resume_from``,
     ``checkpoint_every_steps``, ``state_dir``): save_every: one every that many optimizer steps and at
     each epoch's end, under state_dir (default: the resume directory, else ../checkpoints/state);
@@ -128,7 +132,9 @@ def run(config: Optional[str] = None, *, epochs: Optional[int] = None, checkpoin
     init = build_model(None, model_cfg).state_dict()
     trainer = FiBiNETTrainer(model_cfg, total_steps=n_epochs * steps_per_epoch,
                              batch_size=train_loader.batch_size // world, device=device, rank=rank, world=world,
-                             init_state=init, seed=seed, table_adam=str(model_cfg.get("table_adam", "lazy")))
+                             init_state=init, seed=seed, table_adam=str(model_cfg.get("table_adam", "lazy")),
+                             pos_weight=float(model_cfg.get("loss_pos_weight", 1.0)),
+                             label_smoothing=float(model_cfg.get("loss_label_smoothing", 0.0)))
     del init
     best_auc, history, valid_logloss = 0.0, [], []
     group_by = model_cfg.get("valid_group_by")            # e.g. user_id: also report the per-group AUC

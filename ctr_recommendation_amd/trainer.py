@@ -227,11 +227,19 @@ class FiBiNETTrainer:
                  lazy_window: Optional[int] = None, defer_table_grads: bool = True, max_norm: float = 10.0,
                  optimizer: Optional[str] = None, deterministic: Optional[bool] = None,
                  prefetch_rows: bool = True, shard: Optional[bool] = None, sync_bn: Optional[bool] = None,
-                 native_comm: Optional[bool] = None):
+                 native_comm: Optional[bool] = None, pos_weight: float = 1.0, label_smoothing: float = 0.0):
         self.device = torch.device(device if device is not None else "cuda")
         if self.device.type != "cuda":
             raise RuntimeError("FiBiNETTrainer runs on a HIP device only (no CPU fallback)")
         self.cfg = dict(model_cfg)
+        # the weighted loss (include/fibinet.h, fbn_head_fwd_w): BCEWithLogitsLoss's pos_weight, label
+        # smoothing, and the per-sample weights an optional batch["sample_weight"] (f32 [B]) carries.
+        # Neutral scalars and no such key: the step issues the unweighted head, call for call as before
+        self.pos_weight, self.label_smoothing = float(pos_weight), float(label_smoothing)
+        if not (self.pos_weight > 0.0 and self.pos_weight < float("inf")):
+            raise ValueError(f"pos_weight must be finite and > 0, not {pos_weight!r}")
+        if not 0.0 <= self.label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must lie in [0, 1), not {label_smoothing!r}")
         self.lr = float(lr if lr is not None else model_cfg.get("learning_rate", 1e-3))
         self.wd = float(weight_decay if weight_decay is not None else model_cfg.get("weight_decay", 1e-5))
         # clip_grad_norm_(model.parameters(), max_norm=10.0) (train_fibinet.py:119); settable so
@@ -610,7 +618,8 @@ class FiBiNETTrainer:
                         w16_ready=w16_ready, loss_denom=float(ntot), coll=self.bn_coll, ntot=self._bn_n(ntot, B),
                         acts=self.acts, masks_out=s.masks_out,
                         probe=s.probe, count_batches=False,     # num_batches_tracked: fbn_step_end
-                        after_gather=after_gather)
+                        after_gather=after_gather, pos_weight=self.pos_weight,
+                        label_smoothing=self.label_smoothing)
         gaps = ops.backward(self.p, s.batch, a, a["gout"], self.g, cfg, pos=pos, coll=self.bn_coll,
                             ntot=self._bn_n(ntot, B),
                             extra_sums=[(a["loss_terms"], B, 1, self.loss, 1.0 / ntot)], probe=s.probe,
@@ -1109,7 +1118,7 @@ class FiBiNETTrainer:
             seg.begin()
             a = ops.forward(self.p, sb, cfg, self.rng, table_rows=x.rows_buf, pos=sp, err=self.err, labels=sl,
                             loss_denom=float(ntot), coll=bn, ntot=self._bn_n(ntot, B), acts=self.acts,
-                            count_batches=False)
+                            count_batches=False, pos_weight=self.pos_weight, label_smoothing=self.label_smoothing)
             hooks = {"after_fields_bwd": lambda: seg.call(self._grad_xchg_start)} if self._early_grad_xchg() else None
             ops.backward(self.p, sb, a, a["gout"], self.g, cfg, pos=sp, sendbuf=x.send_buf, coll=bn,
                          ntot=self._bn_n(ntot, B), extra_sums=[(a["loss_terms"], B, 1, self.loss, 1.0 / ntot)],
@@ -1299,10 +1308,15 @@ class FiBiNETTrainer:
         """Raise what the reference would have raised since the last check (one 4-byte read):
         IndexError for an id outside its table (nn.Embedding), ValueError for a step past
         total_steps (OneCycleLR) -- the latter is how graph replays, which never pass through
-        step()'s host-side guard, report it (the device step counter saturates)."""
+        step()'s host-side guard, report it (the device step counter saturates) -- and ValueError for a
+        sample weight that was NaN, infinite or negative (its sample was left out of the loss and the
+        gradient: nothing non-finite reached the optimizer)."""
         e = int(self.err.item())
         if e & 1:
             raise IndexError("index out of range in self (item/likes/views id outside its embedding table)")
+        if e & _lib.FBN_ERR_BIT_WEIGHT:
+            raise ValueError("batch['sample_weight'] held a NaN, infinite or negative weight (those samples were "
+                             "left out of the loss and the gradient)")
         if e & 2:
             raise ValueError(f"Tried to step more than {self.total_steps} times. The specified number of total steps "
                              f"is {self.total_steps}")
@@ -1429,6 +1443,8 @@ class FiBiNETTrainer:
     # "lazy" and "eager" are bit-identical and may differ between save and load)
     _STATE_CHECKED = ("d", "V", "L", "world", "rank", "rows_lo", "rows_local", "total_steps", "lr", "wd", "optimizer",
                       "beta2", "eps", "max_norm", "compute_dtype", "bilinear_type", "R", "sync_bn")
+    # the loss options: a state saved before they existed loads as neutral
+    _STATE_LOSS = {"pos_weight": 1.0, "label_smoothing": 0.0}
 
     def _state_meta(self) -> Dict:
         c = self.fcfg
@@ -1439,7 +1455,8 @@ class FiBiNETTrainer:
                 "beta2": float(self.beta2), "eps": float(self.eps), "max_norm": float(self.max_norm),
                 "compute_dtype": "bf16" if c.bf16 else ("bf16_fwd" if c.fwd16 else "fp32"),
                 "bilinear_type": "each" if c.bilinear_each else "all", "R": int(c.R),
-                "deterministic": bool(self.deterministic), "sync_bn": bool(self.sync_bn)}
+                "deterministic": bool(self.deterministic), "sync_bn": bool(self.sync_bn),
+                "pos_weight": float(self.pos_weight), "label_smoothing": float(self.label_smoothing)}
 
     def _state_tensors(self) -> Dict[str, torch.Tensor]:
         """name -> device tensor of everything a later step reads once the lazy table Adam is flushed."""
@@ -1493,6 +1510,10 @@ class FiBiNETTrainer:
                     if k in ("world", "rank", "rows_lo", "rows_local") else ""
                 raise ValueError(f"training state does not fit this trainer: {k} is {meta.get(k)!r} in the state, "
                                  f"{mine[k]!r} here{hint}")
+        for k, neutral in self._STATE_LOSS.items():
+            if float(meta.get(k, neutral)) != mine[k]:
+                raise ValueError(f"training state does not fit this trainer: {k} is {meta.get(k, neutral)!r} in the "
+                                 f"state, {mine[k]!r} here")
         if (meta.get("table_adam") == "sparse") != (self.table_adam == "sparse"):
             raise ValueError(f"training state does not fit this trainer: table_adam is {meta.get('table_adam')!r} in "
                              f"the state, {self.table_adam!r} here (only 'lazy' and 'eager' are interchangeable)")

@@ -15,7 +15,8 @@
  *    global mutable state except a thread-local error string -> reentrant, graph-capturable.
  *  - return 0 on success, otherwise FBN_ERR_*; fbn_last_error() describes the failure.
  *  - id range violations never fault: kernels set a sticky int flag (*err) that the caller
- *    checks lazily (the reference raises IndexError in nn.Embedding).
+ *    checks lazily (the reference raises IndexError in nn.Embedding).  Bits of the trainer's word:
+ *    1 an id outside its table, 2 a step past total_steps, 4 (FBN_ERR_BIT_WEIGHT) a bad sample weight.
  *  - fp32 storage everywhere; `bf16` flags select bf16 MFMA operands with fp32 accumulation.
  */
 #ifndef FIBINET_H
@@ -258,6 +259,14 @@ int fbn_bn_act_head_fwd(const float* X, float* Y, int B, int C, const float* mea
                         unsigned char* mask_out, const unsigned char* mask_in, const float* hw, const float* hbias,
                         float* logits, float* probs, const float* labels, float* loss_terms, float* gout, float denom,
                         double* bwd_part, float bwd_scale, void* stream);
+/* fbn_bn_act_head_fwd with fbn_head_fwd_w's weighted loss (the same four extra arguments, the same
+ * checks); bwd_part is computed from the weighted gout. */
+int fbn_bn_act_head_fwd_w(const float* X, float* Y, int B, int C, const float* mean, const float* invstd,
+                          const float* g, const float* b, float p_drop, const unsigned long long* rng,
+                          unsigned stream_id, unsigned char* mask_out, const unsigned char* mask_in, const float* hw,
+                          const float* hbias, float* logits, float* probs, const float* labels, float* loss_terms,
+                          float* gout, float denom, double* bwd_part, float bwd_scale, const float* sample_w,
+                          float pos_weight, float label_smoothing, int* err, void* stream);
 int fbn_bn_bwd_reduce(const float* G, const float* gvec, const float* w, const float* hact, float scale,
                       const float* Xpre, const float* mean, int B, int C, double* red_d, void* ws, void* stream);
 int fbn_bn_bwd_apply(const float* G, const float* gvec, const float* w, const float* hact, float scale,
@@ -320,6 +329,22 @@ int fbn_sum_jobs_sq(const void* jobs, int n, const void* slabs, int ns, const vo
  * Replaces src/model_fibinet.py:134,136,199 and nn.BCELoss fwd/bwd (src/train_fibinet.py:79,115). */
 int fbn_head_fwd(const float* H, const float* w, const float* bias, int B, int C, float* logits, float* probs,
                  const float* labels, float* loss_terms, float* gout, float denom, void* stream);
+/* fbn_head_fwd with the weighted loss (BCELoss(weight=) / BCEWithLogitsLoss(pos_weight=) / label
+ * smoothing).  With p = sigmoid(o), t the label, w = sample_w[i] (null: 1), pi = pos_weight,
+ * eps = label_smoothing and n = denom:
+ *   t~    = t (1 - eps) + eps / 2
+ *   term  = w * -(pi t~ max(log p, -100) + (1 - t~) max(log(1 - p), -100))        -> loss_terms[i]
+ *   num   = (1 - t~) p - pi t~ (1 - p)
+ *   gout  = (w num / max(p (1 - p), 1e-12) / n) * (1 - p) * p
+ * (the loss is sum term / n: a mean over samples, not divided by sum w).  At w = 1, pi = 1, eps = 0 and
+ * t in {0, 1} every output equals fbn_head_fwd's bit for bit.  A weight that is NaN, infinite or
+ * negative sets FBN_ERR_BIT_WEIGHT in the sticky *err (may be null) and its row's term and gout are
+ * 0; nothing faults.  pos_weight must be finite and > 0 and label_smoothing in [0, 1): FBN_ERR_ARG
+ * before any launch otherwise. */
+#define FBN_ERR_BIT_WEIGHT 4
+int fbn_head_fwd_w(const float* H, const float* w, const float* bias, int B, int C, float* logits, float* probs,
+                   const float* labels, float* loss_terms, float* gout, float denom, const float* sample_w,
+                   float pos_weight, float label_smoothing, int* err, void* stream);
 int fbn_sigmoid_bwd(const float* gp, const float* probs, float* gout, int B, void* stream);
 int fbn_outer(const float* g, const float* w, float* out, int B, int C, void* stream);
 int fbn_sum(const float* x, int n, float* out, float scale, void* stream);
@@ -665,6 +690,10 @@ int fbn_collate(const int64_t* perm, int B, const int64_t* item, const int64_t* 
 /* x[0:n] = 0 when *flag != 0: the inference collator's whole-batch zero fallback
  * (src/Prediction.py:39-42) on the batch's own missing flag, with no host round trip. */
 int fbn_collate_zero_if(float* x, long long n, const int* flag, void* stream);
+/* out[i] = src[rows[i]] for i < B: one more f32 column of the dataset (src [n], the sample weights)
+ * gathered at the batch's rows, a launch after fbn_collate.  A row outside [0, n) reads nothing and
+ * gives NaN, which the weighted head reports (FBN_ERR_BIT_WEIGHT). */
+int fbn_collate_f32(const int64_t* rows, int B, const float* src, long long n, float* out, void* stream);
 
 /* ---------------------------------------------------------------- device metrics (exact AUC + log-loss)
  * Replaces the validation metric of src/train_fibinet.py:133-146 (every batch's probabilities copied
