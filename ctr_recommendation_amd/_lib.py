@@ -1,5 +1,8 @@
 """ctypes binding of libfibinet_hip.so (the C-ABI declared in include/fibinet.h).
 
+The header is read at import (abi.py): SIGNATURES -- every entry point's ctypes argument types -- and
+the FBN_* constants (module attributes) are derived from it, so no prototype or value is written down twice.
+
 The library is loaded once; a missing or un-loadable library raises immediately -- there is
 no CPU fallback anywhere in the product path.  Every call goes through :func:`call`, which
 raises ``RuntimeError`` with ``fbn_last_error()`` on a non-zero return code.
@@ -15,6 +18,8 @@ from typing import Optional
 
 import torch
 
+from . import abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FBN_LIB_PATH") or os.path.join(_HERE, "libfibinet_hip.so")   # override: tuning tools
 
@@ -26,193 +31,26 @@ D = ctypes.c_double
 SZ = ctypes.c_size_t
 U = ctypes.c_uint
 
-# name -> (restype, argtypes); the single source of truth mirrored by include/fibinet.h
-SIGNATURES = {
-    "fbn_version": (I, []),
-    "fbn_last_error": (ctypes.c_char_p, []),
-    "fbn_device_ok": (I, []),
-    "fbn_gemm_workspace_size": (SZ, [I, I, I, I]),
-    "fbn_gemm": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, F, I, I, I, P, P, SZ, P]),
-    "fbn_gemm_split": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, F, P, P, SZ, P, I, I, P, I, I, P]),
-    "fbn_gemm_bf16out": (I, [P, P, P, I, I, I, I, I, I, I, I, P]),
-    "fbn_gemm_s3": (I, [P, P, P, I, I, I, I, I, I, I, I, LL, LL, F, P, SZ, P]),
-    "fbn_gemm_bn_bwd_part_supported": (I, [I, I, I, I, I, I, I]),
-    "fbn_gemm_bn_bwd_part": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P, P, F, P, P]),
-    "fbn_bn_tile_stats": (I, [P, I, I, P, P, P]),
-    "fbn_bn_tile_moments": (I, [P, I, I, P, P]),
-    "fbn_bn_moments_finalize": (I, [P, D, I, P, P, P, P, F, F, I, P]),
-    "fbn_bn_tile_finalize": (I, [P, I, I, D, P, P, P, P, F, F, I, P]),
-    "fbn_bn_colpart_size": (SZ, [I, I]),
-    "fbn_row_chunks": (I, [I]),
-    "fbn_bn_bwd_chunks": (I, [I, I]),
-    "fbn_bn_bwd_fused": (I, [P, P, P, P, P, F, P, P, P, P, I, I, D, P, P, P, P, P, P, P, P, P]),
-    "fbn_bn_bwd_fused_img": (I, [P, P, P, P, P, F, P, P, P, P, I, I, D, P, P, P, P, P, P, P, P, P]),
-    "fbn_colsum_partial": (I, [P, I, I, I, P, P]),
-    "fbn_sum_jobs": (I, [P, I, P]),
-    "fbn_sum_jobs2": (I, [P, I, P, I, P]),
-    "fbn_sum_jobs_sq": (I, [P, I, P, I, P, I, P, P]),
-    "fbn_gemm_slabs_size": (SZ, [I, I, I]),
-    "fbn_gemm_slabs": (I, [P, P, I, I, I, I, I, I, I, P, SZ, P, I, I, P, I, I, P, P]),
-    "fbn_gemm_slabs_split": (I, [I, I, I]),
-    "fbn_gemm_slabs_group": (I, [P, I, P]),
-    "fbn_gemm_slabs_group_split": (I, [I, I, I]),
-    "fbn_fields_fwd": (I, [P, P, P, P, P, P, P, F, P, I, P, LL, P, P, P, P, P, I, P, P, P, P, I, I, P, P, P, P, P, I, I, I, I,
-                           P]),
-    "fbn_fields_fwd_hot": (I, [P, P, P, P, P, P, P, F, P, I, P, LL, P, P, P, P, I, P, P, P, P, I, I, P, P, P, P, P,
-                               I, I, I, P, P, I, P]),
-    "fbn_hot_rows": (I, [P, P, I, I, LL, P, P, P, I, I, I, P]),
-    "fbn_fields_bwd_partials_size": (I, [I, I, I]),
-    "fbn_fields_bwd_grid": (I, [I, I]),
-    "fbn_fields_bwd": (I, [P, P, P, P, P, P, P, F, P, P, P, I, I, P, P, P, P, P, P, P, P, P, P, P, P, LL, P, P, I, I,
-                           I, I, P]),
-    "fbn_fields_bwd_img": (I, [P, P, P, P, P, P, P, F, P, P, P, I, I, P, P, P, P, P, P, P, P, P, P, P, P, LL, P, P, I,
-                               I, I, I, P]),
-    "fbn_fields_bwd_slot": (I, [P, P, P, P, P, P, P, F, P, P, P, I, I, P, P, P, P, P, P, P, I, P, P, P, I, LL, P, P, P,
-                                LL, I, I, I, P]),
-    "fbn_pairs_fwd": (I, [P, P, P, P, I, I, I, I, I, P]),
-    "fbn_pairs_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I, P]),
-    "fbn_pairs_fwd_img": (I, [P, P, P, P, I, I, I, P]),
-    "fbn_pairs_bwd_img": (I, [P, P, P, P, P, I, I, I, P]),
-    "fbn_bn_workspace_size": (SZ, [I, I]),
-    "fbn_bn_stats_pass": (I, [P, I, I, P, P, P, P]),
-    "fbn_bn_mean": (I, [P, D, I, P, P]),
-    "fbn_bn_finalize": (I, [P, P, D, I, P, P, P, P, F, F, I, P]),
-    "fbn_bn_stats": (I, [P, I, I, P, P, P, P, F, F, I, P, P]),
-    "fbn_bn_eval_params": (I, [P, P, P, P, I, F, P]),
-    "fbn_bn_act_fwd": (I, [P, P, I, I, P, P, P, P, F, P, U, P, P, P, P]),
-    "fbn_bn_act_fwd_img": (I, [P, P, I, I, P, P, P, P, F, P, U, P, P, P, P]),
-    "fbn_bn_act_head_fwd": (I, [P, P, I, I, P, P, P, P, F, P, U, P, P, P, P, P, P, P, P, P, F, P, F, P]),
-    "fbn_bn_act_head_fwd_w": (I, [P, P, I, I, P, P, P, P, F, P, U, P, P, P, P, P, P, P, P, P, F, P, F, P, F, F, P,
-                                  P]),
-    "fbn_bn_bwd_reduce": (I, [P, P, P, P, F, P, P, I, I, P, P, P]),
-    "fbn_bn_bwd_apply": (I, [P, P, P, P, F, P, P, P, P, I, I, P, D, P, P, P, P, P, P, P]),
-    "fbn_convert_bf16": (I, [P, I, P]),
-    "fbn_bn_bwd": (I, [P, P, P, P, F, P, P, P, P, I, I, P, P, P, P, P, P]),
-    "fbn_colsum_workspace_size": (SZ, [I, I]),
-    "fbn_colsum": (I, [P, I, I, I, P, F, P, P]),
-    "fbn_head_fwd": (I, [P, P, P, I, I, P, P, P, P, P, F, P]),
-    "fbn_head_fwd_w": (I, [P, P, P, I, I, P, P, P, P, P, F, P, F, F, P, P]),
-    "fbn_sigmoid_bwd": (I, [P, P, P, I, P]),
-    "fbn_outer": (I, [P, P, P, I, I, P]),
-    "fbn_sum": (I, [P, I, P, F, P]),
-    "fbn_sumsq": (I, [P, LL, P, I, P, P]),
-    "fbn_clip_coef": (I, [P, F, P, P, P]),
-    "fbn_adam_dense": (I, [P, P, P, P, LL, P, P, P, F, F, F, P, F, P, P, P]),
-    "fbn_sparse_fixup": (I, [P, P, P, I, I, LL, I, P, P, P, P, I, I, P]),
-    "fbn_sumsq_sparse": (I, [P, P, P, I, I, I, P, P]),
-    "fbn_sparse_fixup_dup": (I, [P, I, P, P, P, I, I, P]),
-    "fbn_sumsq_sparse_norms": (I, [P, P, P, P, I, I, I, P, P, P, LL, P]),
-    "fbn_sparse_fold_fx": (I, [P, P, I, P, P, I, I, P, P]),
-    "fbn_adam_table": (I, [P, P, P, LL, I, P, P, P, P, I, P, P, P, F, F, F, I, P]),
-    "fbn_adam_touched": (I, [P, P, P, I, P, P, P, P, I, I, P, P, P, F, F, F, P, P]),
-    "fbn_adam_catchup": (I, [P, P, P, LL, I, P, I, P, I, I, P, P, P, F, F, F, P, P, P, LL, I, I, P]),
-    "fbn_adam_claim_catchup": (I, [P, P, I, I, LL, P, P, P, P, P, P, P, P, LL, I, I, P, P, P, F, F, F, P, P, P, LL, I,
-                                   I, P]),
-    "fbn_adam_claim_catchup_conv": (I, [P, P, I, I, LL, P, P, P, P, P, P, P, P, LL, I, I, P, P, P, F, F, F, P, P, P,
-                                        LL, I, I, P, I, P]),
-    "fbn_adam_flush": (I, [P, P, P, LL, I, P, P, P, F, F, F, P, P, P, LL, I, I, P]),
-    "fbn_adam_prefetch_rows": (I, [P, I, I, LL, P, P, P, P, P, I, P, P, P, F, F, F, P, P, P, LL, I, I, P]),
-    "fbn_adam_prefetch": (I, [P, P, I, I, LL, P, P, P, P, P, I, P, P, P, F, F, F, P, P, P, LL, I, I, P]),
-    "fbn_adam_prefetch_binned_ws_size": (SZ, [LL]),
-    "fbn_adam_prefetch_binned": (I, [P, P, I, I, LL, P, P, P, P, P, I, P, P, P, F, F, F, P, P, P, LL, I, I, P, SZ, P]),
-    "fbn_adam_selftest": (I, [I, ctypes.c_uint, P, P]),
-    "fbn_adam_step_tail": (I, [P, P, P, P, LL, P, F, P, P, P, P, P, I, P, P, P, P, I, I, P, P, F, F, F, P, P, P, P, I,
-                               LL, I, P, P, P, P, I, P, P]),
-    "fbn_adam_commit": (I, [P, P, P, I, P, P, P, P, I, I, P, P, P, F, F, F, P, P, P, P, I, I, P]),
-    "fbn_claim_rows": (I, [P, P, I, I, LL, P, P, P, P, P]),
-    "fbn_pack_extras": (I, [P, P, P, P]),
-    "fbn_unpack_extras": (I, [P, P, P, P]),
-    "fbn_unpack_sumsq": (I, [P, P, P, LL, P, P]),
-    "fbn_step_end": (I, [P, P, P, P, P, I, P, P]),
-    "fbn_route": (I, [P, P, I, I, LL, LL, I, P, P, P, P, P, P, P]),
-    "fbn_route_fc": (I, [P, P, I, I, LL, LL, I, I, P, P, P, P, P]),
-    "fbn_route_fc_status": (I, [P, P, I, I, I, P, P, P]),
-    "fbn_ring_slot": (I, [P, I, LL, P, P, P, I, LL, P, LL, LL, P]),
-    "fbn_owner_gather_self": (I, [P, I, P, P, P, P, I, I, I, P, I, I, P]),
-    "fbn_adam_owner_claim_catchup": (I, [P, I, I, P, P, P, P, P, P, LL, I, I, P, P, P, F, F, F, P, P, P, LL, I, I,
-                                         P]),
-    "fbn_owner_fold": (I, [P, I, I, P, P, P, I, P, LL, LL, P, I, LL, P, P, P, I, P, P, P]),
-    "fbn_sumsq_flagged": (I, [P, I, P, P, I, P, P, P, I, P]),
-    "fbn_owner_claim": (I, [P, I, P, P, I, P]),
-    "fbn_owner_gather": (I, [P, I, P, P, P, P, I, I, I, P]),
-    "fbn_widen_bf16": (I, [P, P, LL, P]),
-    "fbn_pad_routes": (I, [P, P, P, I, I, P, P]),
-    "fbn_compact_routes": (I, [P, I, I, P, P, P]),
-    "fbn_copy_jobs": (I, [P, P, P, I, P]),
-    "fbn_bilinear_supported": (I, [I]),
-    "fbn_bilinear_fwd": (I, [P, P, P, I, I, I, P]),
-    "fbn_bilinear_bwd": (I, [P, I, I, P, P, P, P, P, I, I, P]),
-    "fbn_bilinear_fields_bwd_supported": (I, [I, I, I, I]),
-    "fbn_bilinear_fields_bwd": (I, [P, I, P, P, P, P, P, P, P, P, P, F, P, P, P, I, I, P, P, P, P, P, P, P, P, P, P, P,
-                                    I, LL, P, I, I, P]),
-    "fbn_collate": (I, [P, I, P, P, I, I, P, P, P, P, P, LL, P, P, I, P, P, P, P, P, P, P, P, P]),
-    "fbn_collate_zero_if": (I, [P, LL, P, P]),
-    "fbn_collate_f32": (I, [P, I, P, LL, P, P]),
-    "fbn_eval_pack": (I, [P, P, LL, P, P, P]),
-    "fbn_eval_workspace_size": (SZ, [LL]),
-    "fbn_eval_reduce": (I, [P, LL, P, SZ, P, P, P]),
-    "fbn_sort_u64_workspace_size": (SZ, [LL]),
-    "fbn_sort_u64": (I, [P, LL, I, P, SZ, P, P]),
-    "fbn_digest_u64": (I, [P, LL, ctypes.c_ulonglong, P, P]),
-    "fbn_eval_pack_groups": (I, [P, LL, P, P, P]),
-    "fbn_gauc_workspace_size": (SZ, [LL]),
-    "fbn_gauc_reduce": (I, [P, P, LL, P, SZ, P, P, P, P]),
-    "fbn_calib_workspace_size": (SZ, [LL]),
-    "fbn_calib_reduce": (I, [P, LL, I, P, SZ, P, P, P]),
-    "fbn_isotonic_workspace_size": (SZ, [LL]),
-    "fbn_isotonic_max_blocks": (LL, [LL]),
-    "fbn_isotonic_fit": (I, [P, LL, P, SZ, P, LL, P, P]),
-    "fbn_isotonic_apply": (I, [P, LL, P, I, P, P]),
-    "fbn_auc_place_workspace_size": (SZ, [LL]),
-    "fbn_auc_place": (I, [P, LL, P, SZ, P, P, P]),
-    "fbn_delong_reduce": (I, [P, P, P, P, LL, P, P, P]),
-    "fbn_rec_item_cache": (I, [P, P, P, P, P, P, F, I, LL, P, P, I, I, P]),
-    "fbn_rec_hist_pool": (I, [P, P, LL, P, P, I, I, I, P]),
-    "fbn_rec_fields": (I, [P, P, P, P, P, P, I, P, LL, P, P, P, P, I, P, P, P, I, I, P, P, I, I, I, I, P]),
-    "fbn_rec_topk_workspace_size": (SZ, [I, I, I]),
-    "fbn_rec_topk": (I, [P, I, I, I, P, P, I, I, I, P, P, SZ, P, P, P, P, P, P]),
-    "fbn_rec_rank": (I, [P, I, I, I, P, P, I, I, P, P, P, P, P]),
-    "fbn_rank_hist": (I, [P, LL, P, P]),
-    "fbn_rec_fields_list": (I, [P, P, P, P, P, P, I, P, LL, P, P, P, P, I, P, P, P, I, I, P, P, I, P, I, I, I, I, I, P]),
-    "fbn_rec_topk_list": (I, [P, I, I, I, P, I, I, P, P, I, I, I, P, P, SZ, P, P, P, P, P, P, P]),
-    "fbn_rec_rank_list": (I, [P, I, I, I, P, I, I, P, P, I, I, P, P, P, P, P]),
-    "fbn_knn_normalize": (I, [P, I, P, LL, P, I, I, P, P]),
-    "fbn_knn_query_pool": (I, [P, I, I, P, LL, P, I, I, P, P, P]),
-    "fbn_knn_scores": (I, [P, I, P, P, I, I, I, I, I, P, P]),
-    "fbn_plan_create": (I, [P]),
-    "fbn_plan_destroy": (I, [P]),
-    "fbn_plan_size": (I, [P]),
-    "fbn_plan_add_call": (I, [P, ctypes.c_char_p, P, I, P, I]),
-    "fbn_plan_add_record": (I, [P, I, P]),
-    "fbn_plan_add_wait": (I, [P, P, I]),
-    "fbn_plan_run": (I, [P, P]),
-    "fbn_plan_event_sync": (I, [P, I]),
-    "fbn_probe_arm": (I, [I]),
-    "fbn_probe_disarm": (I, []),
-    "fbn_probe_elapsed": (F, [I]),
-    "fbn_comm_load": (I, [ctypes.c_char_p]),
-    "fbn_comm_id_bytes": (I, []),
-    "fbn_comm_unique_id": (I, [P]),
-    "fbn_comm_init": (I, [P, P, I, I]),
-    "fbn_comm_destroy": (I, [P]),
-    "fbn_comm_alltoallv": (I, [P, P, P, P, P, LL, P]),
-    "fbn_comm_alltoall_peers": (I, [P, P, P, LL, P]),
-    "fbn_comm_alltoall": (I, [P, P, P, LL, P]),
-    "fbn_comm_allreduce": (I, [P, P, LL, I, P]),
-    "fbn_comm_allgather": (I, [P, P, P, LL, P]),
-    "fbn_sum_slices": (I, [P, I, LL, I, P, P]),
-    "fbn_comm_watch": (I, [LL]),
-    "fbn_comm_heartbeat": (I, [P]),
-    "fbn_comm_abort": (I, [P]),
-    "fbn_comm_watchdog_fired": (I, [P]),
-}
+_CTYPES = {"int": I, "long long": LL, "float": F, "double": D, "size_t": SZ, "unsigned": U, "unsigned int": U,
+           "unsigned long long": ctypes.c_ulonglong, "const char*": ctypes.c_char_p}
 
-FBN_ERR_BIT_WEIGHT = 4        # include/fibinet.h: sticky *err bit of a NaN, infinite or negative sample weight
-FBN_SORT_TILE = 2048          # include/fibinet.h: keys per workgroup of fbn_sort_u64's passes
-FBN_GAUC_REC_WORDS = 8        # include/fibinet.h: 8-byte words of fbn_gauc_reduce's record
-FBN_CALIB_MAX_BINS = 1024     # include/fibinet.h: bins of fbn_calib_reduce at most
-FBN_CALIB_BIN_WORDS = 8       # include/fibinet.h: 8-byte words per bin of its table
-FBN_DELONG_REC_WORDS = 8      # include/fibinet.h: 8-byte words of fbn_delong_reduce's record
+
+def _ctype(name: str, typ: str):
+    if typ in _CTYPES:
+        return _CTYPES[typ]
+    if typ.endswith("*"):
+        return P
+    raise ValueError(f"{name}: include/fibinet.h uses the type {typ!r}, which has no ctypes mapping")
+
+
+def signatures(decls) -> dict:
+    """name -> (restype, argtypes) of abi.declarations()' entry points."""
+    return {name: (_ctype(name, ret), [_ctype(name, a) for a in args]) for name, ret, args in decls}
+
+
+_decls, CONSTANTS = abi.read_header()
+SIGNATURES = signatures(_decls)
+globals().update(CONSTANTS)         # every #define FBN_X <integer> of the header: _lib.FBN_SORT_TILE, ...
 
 _lib: Optional[ctypes.CDLL] = None
 

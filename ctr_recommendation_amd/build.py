@@ -11,13 +11,12 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
-from . import gen_thunks
-
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 BUILD = os.path.join(ROOT, "build", "fibinet_hip")
 LIB = os.path.join(HERE, "libfibinet_hip.so")
+HEADER = os.path.join(ROOT, "include", "fibinet.h")     # every source includes it: an edit recompiles all
 SOURCES = ["capi.cpp", "gemm.hip", "fields.hip", "mlp.hip", "optim.hip", "exchange.hip", "collate.hip", "bilinear.hip", "metrics.hip",
            "sort.hip", "isotonic.hip", "recommend.hip", "retrieve.hip", "digest.hip", "plan.cpp", "comm.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -29,7 +28,7 @@ FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wno-unused-re
 def _compile(src: str, build_dir: str = BUILD, defines=()) -> str:
     path = os.path.join(CSRC, src)
     obj = os.path.join(build_dir, src + ".o")
-    deps = [path] + [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith((".h", ".inc"))]
+    deps = [path, HEADER] + [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
     if os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(d) for d in deps):
         return obj
     cmd = [HIPCC] + FLAGS + [f"-D{d}" for d in defines] + ["-c", path, "-o", obj]
@@ -44,7 +43,6 @@ def _compile(src: str, build_dir: str = BUILD, defines=()) -> str:
 
 def build(verbose: bool = True) -> str:
     os.makedirs(BUILD, exist_ok=True)
-    gen_thunks.write_if_changed(verbose)     # the step programs' thunks follow include/fibinet.h
     with ThreadPoolExecutor(max_workers=min(8, len(SOURCES))) as ex:
         objs = list(ex.map(_compile, SOURCES))
     newest = max(os.path.getmtime(o) for o in objs)
@@ -74,7 +72,6 @@ VARIANTS = {
 def build_variant(name: str, verbose: bool = True) -> str:
     defines = VARIANTS[name]
     bdir = os.path.join(ROOT, "build", "variant_" + name)
-    gen_thunks.write_if_changed(verbose)
     os.makedirs(bdir, exist_ok=True)
     with ThreadPoolExecutor(max_workers=min(8, len(SOURCES))) as ex:
         objs = list(ex.map(lambda s: _compile(s, bdir, defines), SOURCES))

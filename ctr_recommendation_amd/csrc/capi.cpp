@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
+#include "fibinet.h"
+
 static thread_local char g_err[512] = {0};
 
 void fbn_set_error(const char* msg) {

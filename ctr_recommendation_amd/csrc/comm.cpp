@@ -34,6 +34,8 @@
 #include <set>
 #include <thread>
 
+#include "fibinet.h"
+
 void fbn_set_error(const char* msg);
 
 namespace {

@@ -5,6 +5,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// The C ABI: every entry point's definition is checked against its declaration, and the error codes
+// and the FBN_* constants are the header's (no source defines one again).  By its place in the
+// tree, so that a kernel source still compiles with no include path given.
+#include "../../include/fibinet.h"
+
 // Every kernel of the library is launched through fbn_launch: while the host has a probe armed
 // (fbn_probe_arm .. fbn_probe_disarm around one entry-point call, bench.py's roofline timings) the
 // launch records the probe's start event at the first kernel's start and its stop event at every
@@ -25,17 +30,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
-
-// Error codes shared with include/fibinet.h
-enum {
-  FBN_OK = 0,
-  FBN_ERR_ARG = 1,
-  FBN_ERR_LAUNCH = 2,
-  FBN_ERR_UNSUPPORTED = 3,
-};
-// Bits of the sticky *err word (include/fibinet.h): 1 = an id outside its table, 2 = a step past
-// total_steps, 4 = a sample weight that is NaN, infinite or negative
-#define FBN_ERR_BIT_WEIGHT 4
 
 // round-to-nearest-even f32 -> bf16 (NaN-safe through the hardware cvt at -O3)
 __device__ __forceinline__ short f2bf(float x) {

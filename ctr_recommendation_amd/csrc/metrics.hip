@@ -682,8 +682,6 @@ extern "C" int fbn_gauc_reduce(const uint32_t* keys, const uint32_t* gids, long 
 //                            the range, and the trailing status word
 // Every sum is a u64 integer sum (fx, fx2 <= 2^32 and n < 2^31: below 2^63), so nothing depends on any
 // order; the sort makes the tie split (negatives first) canonical.  No atomics except the status bit.
-#define FBN_CALIB_MAX_BINS 1024                  // include/fibinet.h publishes the same two values
-#define FBN_CALIB_BIN_WORDS 8
 #define CA_REC 4                                 // prefix columns: y, fx, y * fx, fx2
 #define CA_BND 5                                 // words per boundary: rank + the four prefixes
 
@@ -881,7 +879,6 @@ extern "C" int fbn_calib_reduce(const uint32_t* keys, long long n, int bins, voi
 // sum of n < 2^31 of them below 2^95, so the low and the high 32 bits of each product go to two separate
 // u64 sums (each below 2^63, no carries).  Integer atomics, one per workgroup and word: order-independent.
 #define EV_BAD_PAIR 0x20000u                     // status bit 17: the two key sets' labels differ
-#define FBN_DELONG_REC_WORDS 8                   // include/fibinet.h publishes the same value
 #define DL_BLOCKS_MAX 1024
 
 struct PlaceLayout {

@@ -964,7 +964,6 @@ struct SlabJob {
 #define FBN_SUM_WIDE 32        // jobs with at least this many columns take 16 columns per block
 #define FBN_MAX_SLAB_JOBS 8
 #define FBN_SLAB_GROUPS 4      // slab groups per output quad (256 threads = 64 quads x 4 groups)
-#define FBN_SUMSQ_SLOTS 64     // the clip norm's accumulator slots (optim.hip, include/fibinet.h)
 #define FBN_MAX_SQ_RANGES 24   // fbn_sum_jobs_sq: (pointer, count) ranges squared by extra blocks
 #define FBN_SQ_RANGE_BLOCK 1024   // elements of a range per block
 struct SqRange {
@@ -1161,33 +1160,6 @@ __global__ void head_fwd_kernel(const float* __restrict__ H, int B, int C, HeadA
 __global__ void sigmoid_bwd_kernel(const float* gp, const float* probs, float* gout, int B) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < B) gout[i] = gp[i] * (1.f - probs[i]) * probs[i];
-}
-
-// dH[b][c] = g[b] * w[c]   (rank-1; used by the drop-in backward)
-__global__ void outer_kernel(const float* g, const float* w, float* out, int B, int C) {
-  const size_t total = (size_t)B * C;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
-    out[i] = g[i / C] * w[i % C];
-}
-
-// out = scale * sum(x): one 1024-thread block, 4 independent accumulators per thread, wave
-// shuffles + 16-entry LDS stage (fixed order: deterministic)
-__global__ void __launch_bounds__(1024) sum_kernel(const float* x, int n, float* out, float scale) {
-  __shared__ float red[16];
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  int i = threadIdx.x;
-  for (; i + 3 * 1024 < n; i += 4 * 1024) {
-    s0 += x[i]; s1 += x[i + 1024]; s2 += x[i + 2048]; s3 += x[i + 3072];
-  }
-  for (; i < n; i += 1024) s0 += x[i];
-  float s = wave_sum((s0 + s1) + (s2 + s3));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    float t = threadIdx.x < 16 ? red[threadIdx.x] : 0.f;
-    t = wave_sum(t);
-    if (threadIdx.x == 0) out[0] = t * scale;
-  }
 }
 
 // ------------------------------------------------------------------ C ABI
@@ -1541,19 +1513,6 @@ extern "C" int fbn_sigmoid_bwd(const float* gp, const float* probs, float* gout,
   return FBN_OK;
 }
 
-extern "C" int fbn_outer(const float* g, const float* w, float* out, int B, int C, void* stream) {
-  if (B <= 0) return FBN_OK;
-  fbn_launch(outer_kernel, dim3(ew_grid((size_t)B * C)), dim3(256), 0, (hipStream_t)stream, g, w, out, B, C);
-  FBN_CHECK_LAUNCH();
-  return FBN_OK;
-}
-
-extern "C" int fbn_sum(const float* x, int n, float* out, float scale, void* stream) {
-  fbn_launch(sum_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, x, n, out, scale);
-  FBN_CHECK_LAUNCH();
-  return FBN_OK;
-}
-
 // ------------------------------------------------------------------ bf16 weight copies
 // out[i*dld + j] = bf16( T ? src[j*ld + rm(i)] : src[i*ld + rm(j)] ) (or its rounding residual, part 1),
 // i < rows, j < cols, rm(x) = x + (x < seg ? off0 : off1).  Up to 16 jobs per launch: the compacted /
@@ -1699,19 +1658,19 @@ extern "C" int fbn_row_chunks(int B) { return row_chunks(B); }
 // (N, ldc, seg, off0, off1 multiples of 4; out 16-B aligned).  One launch for both.
 static int sum_jobs_impl(const SumJob* jobs, int n, const SlabJob* slabs, int ns, const SqRange* ranges, int nr,
                          double* sumsq, void* stream);
-extern "C" int fbn_sum_jobs2(const SumJob* jobs, int n, const SlabJob* slabs, int ns, void* stream) {
-  return sum_jobs_impl(jobs, n, slabs, ns, nullptr, 0, nullptr, stream);
+extern "C" int fbn_sum_jobs2(const void* jobs, int n, const void* slabs, int ns, void* stream) {
+  return sum_jobs_impl((const SumJob*)jobs, n, (const SlabJob*)slabs, ns, nullptr, 0, nullptr, stream);
 }
 // fbn_sum_jobs2 with the clip norm's dense part: the squares of the outputs of the sum jobs with sq = 1
 // and of every slab job, and of the nr (<= 24) ranges {pointer, count} (host array; dense gradients this
 // launch does not produce, final before it), added to the norm slots sumsq[FBN_SUMSQ_SLOTS] in f64.
-extern "C" int fbn_sum_jobs_sq(const SumJob* jobs, int n, const SlabJob* slabs, int ns, const SqRange* ranges, int nr,
+extern "C" int fbn_sum_jobs_sq(const void* jobs, int n, const void* slabs, int ns, const void* ranges, int nr,
                                double* sumsq, void* stream) {
   if (!sumsq || nr < 0 || nr > FBN_MAX_SQ_RANGES || (nr > 0 && !ranges)) {
     fbn_set_error("fbn_sum_jobs_sq: sumsq and at most 24 ranges");
     return FBN_ERR_ARG;
   }
-  return sum_jobs_impl(jobs, n, slabs, ns, ranges, nr, sumsq, stream);
+  return sum_jobs_impl((const SumJob*)jobs, n, (const SlabJob*)slabs, ns, (const SqRange*)ranges, nr, sumsq, stream);
 }
 static int sum_jobs_impl(const SumJob* jobs, int n, const SlabJob* slabs, int ns, const SqRange* ranges, int nr,
                          double* sumsq, void* stream) {
@@ -1765,7 +1724,7 @@ static int sum_jobs_impl(const SumJob* jobs, int n, const SlabJob* slabs, int ns
   return FBN_OK;
 }
 
-extern "C" int fbn_sum_jobs(const SumJob* jobs, int n, void* stream) {
+extern "C" int fbn_sum_jobs(const void* jobs, int n, void* stream) {
   if (n <= 0) return FBN_OK;
   return fbn_sum_jobs2(jobs, n, nullptr, 0, stream);
 }

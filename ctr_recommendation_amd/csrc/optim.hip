@@ -23,7 +23,6 @@
 
 // squared-norm accumulators: FBN_SUMSQ_SLOTS doubles, block b adds into slot b % SLOTS (one
 // address per block would serialise the returning-free f64 atomics of thousands of blocks)
-#define FBN_SUMSQ_SLOTS 64
 
 struct AdamConsts {
   float w1;     // 1 - beta1 (as float)
@@ -220,16 +219,12 @@ __global__ void adam_dense_kernel(float* __restrict__ p, const float* __restrict
 #define FBN_SLOT_FLAG 0x40000000
 // Lp1 | FBN_GRAD_FULL (deterministic mode): extra[e] of a flagged claimer holds the row's FULL
 // gradient (fbn_sparse_fold_fx), not the sum of its duplicates
-#define FBN_GRAD_FULL 0x10000
 // Lp1 | FBN_GRAD_CELL: `vec` is the address of a device cell holding the row pointer (fbn_ring_slot:
 // the owner's received gradient rows in deferred-gradient ring slot step % ring_n, a slot chosen on
 // the device, so a recorded step program needs no host-side ring index)
-#define FBN_GRAD_CELL 0x20000
 // Lp1 | FBN_GRAD_BF16 (Lp1 == 1 only): the per-entry rows are bf16 (the sharded owner's bf16 deferred-
 // gradient ring: the bf16 mode's wire rows kept as they arrived; widened on every read)
-#define FBN_GRAD_BF16 0x40000
 // ring_n | FBN_RING_BF16 (PendSrc, fbn_owner_fold): the deferred-gradient ring holds bf16 rows
-#define FBN_RING_BF16 0x40000000
 #define FBN_FOLD_CHUNKS 1     // sparse_fixup_dup_kernel: 64-entry chunks per wave
 #define FBN_FOLD_THREADS 1024 // sparse_fixup_dup_kernel: 16 waves share one LDS table
 struct GradSrc {
@@ -812,6 +807,7 @@ extern "C" int fbn_adam_selftest(int n, unsigned seed, unsigned long long* dev, 
 // pend = base + 12 B; each field is indexed with the record stride below.
 #define FBN_RS_I 4   // record stride in ints
 #define FBN_RS_Q 2   // in u64
+static_assert(FBN_RS_I * 4 == FBN_ROW_STATE_BYTES && FBN_RS_Q * 8 == FBN_ROW_STATE_BYTES, "the header's record size");
 // the whole record of row r from its `last` field pointer: {tag lo, tag hi, last, pend}
 __device__ __forceinline__ int4 row_state(const int* last, long long r) {
   return *reinterpret_cast<const int4*>(last + (size_t)r * FBN_RS_I - 2);
@@ -1814,6 +1810,7 @@ __global__ void __launch_bounds__(256) adam_commit_kernel(float* __restrict__ p,
 // the rest the deferred-gradient commit; the last block to finish (ticket counter) advances the
 // step, the dropout offset and num_batches_tracked and clears the norm slots (fbn_step_end).
 #define FBN_TICKET_GROUPS 16   // fbn_adam_step_tail: ticket is [1 + FBN_TICKET_GROUPS] words
+static_assert(1 + FBN_TICKET_GROUPS == FBN_TICKET_WORDS, "the ticket words the header tells the caller to allocate");
 struct StepEnd {
   int* step;
   unsigned long long* rng;

@@ -8,18 +8,20 @@
 // edges) while running it, and replays them natively: the same launches on the same streams in
 // the same order, so a replay is bit-identical to the eager step it was recorded from.
 //
-// Replay calls each recorded entry point through a packed-argument thunk generated from
-// include/fibinet.h (csrc/plan_thunks.inc, ctr_recommendation_amd/gen_thunks.py): the thunk
-// takes the recorded arguments as two arrays -- integer-class values (pointers, int, long long,
-// size_t) as 64-bit words, float / double values as doubles (a float in the low 32 bits of its
-// double) -- and makes an ordinary, well-typed call of the entry point's declared prototype.
-// A recording names the entry point; its argument counts are checked against the thunk's.
+// Replay calls each recorded entry point through a packed-argument thunk that the compiler makes
+// from the prototype include/fibinet.h declares (template Thunk below; one table line per
+// recordable entry point): the thunk takes the recorded arguments as two arrays -- integer-class
+// values (pointers, int, long long, size_t) as 64-bit words, float / double values as doubles (a
+// float in the low 32 bits of its double) -- and makes an ordinary, well-typed call of the entry
+// point.  A recording names the entry point; its argument counts are checked against the thunk's.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "fibinet.h"
@@ -50,7 +52,195 @@ inline float plan_f32(double d) {
   return x;
 }
 
-#include "plan_thunks.inc"
+// The thunk of entry point Fn, from its prototype int (A...): argument k is slot(k) of its class's
+// array, where slot(k) counts the earlier arguments of the same class.
+template <auto Fn>
+struct Thunk;
+template <class... A, int (*Fn)(A...)>
+struct Thunk<Fn> {
+  template <class T>
+  static constexpr bool is_flt = std::is_floating_point<T>::value;
+  static constexpr int nf = (0 + ... + int(is_flt<A>));
+  static constexpr int ni = int(sizeof...(A)) - nf;
+  static_assert(ni <= kMaxInt && nf <= kMaxFlt, "an Op cannot hold this entry point's arguments");
+
+  static constexpr int slot(int k) {
+    constexpr bool flt[] = {is_flt<A>..., false};
+    int n = 0;
+    for (int j = 0; j < k; ++j) n += flt[j] == flt[k];
+    return n;
+  }
+  template <class T, int K>
+  static T arg(const U* i, const double* f) {
+    if constexpr (std::is_same<T, float>::value) return plan_f32(f[K]);
+    else if constexpr (std::is_same<T, double>::value) return f[K];
+    else if constexpr (std::is_pointer<T>::value) return reinterpret_cast<T>(static_cast<uintptr_t>(i[K]));
+    else return static_cast<T>(i[K]);
+  }
+  template <size_t... K>
+  static int call(const U* i, const double* f, std::index_sequence<K...>) {
+    (void)i, (void)f;
+    return Fn(arg<A, slot(K)>(i, f)...);
+  }
+  static int run(const U* i, const double* f) { return call(i, f, std::index_sequence_for<A...>{}); }
+};
+
+// fbn_adam_catchup's arguments 13..15 (wd, beta2, eps) are floats between integers
+static_assert(Thunk<fbn_adam_catchup>::ni == 20 && Thunk<fbn_adam_catchup>::nf == 3, "argument classes");
+static_assert(Thunk<fbn_adam_catchup>::slot(12) == 12 && Thunk<fbn_adam_catchup>::slot(13) == 0 &&
+                  Thunk<fbn_adam_catchup>::slot(15) == 2 && Thunk<fbn_adam_catchup>::slot(16) == 13,
+              "a slot counts the earlier arguments of its own class only");
+static_assert(Thunk<fbn_probe_disarm>::ni == 0 && Thunk<fbn_probe_disarm>::nf == 0, "no arguments");
+
+// Every int-returning entry point a step program may replay: all but the program machinery itself
+// (fbn_plan_*) and the communicator's setup and watchdog calls.  Sorted by name (find_thunk).
+#define FBN_THUNK(fn) {#fn, Thunk<fn>::run, Thunk<fn>::ni, Thunk<fn>::nf}
+constexpr PlanThunk kPlanThunks[] = {
+    FBN_THUNK(fbn_adam_catchup),
+    FBN_THUNK(fbn_adam_claim_catchup),
+    FBN_THUNK(fbn_adam_claim_catchup_conv),
+    FBN_THUNK(fbn_adam_commit),
+    FBN_THUNK(fbn_adam_dense),
+    FBN_THUNK(fbn_adam_flush),
+    FBN_THUNK(fbn_adam_owner_claim_catchup),
+    FBN_THUNK(fbn_adam_prefetch),
+    FBN_THUNK(fbn_adam_prefetch_binned),
+    FBN_THUNK(fbn_adam_prefetch_rows),
+    FBN_THUNK(fbn_adam_selftest),
+    FBN_THUNK(fbn_adam_step_tail),
+    FBN_THUNK(fbn_adam_table),
+    FBN_THUNK(fbn_adam_touched),
+    FBN_THUNK(fbn_auc_place),
+    FBN_THUNK(fbn_bilinear_bwd),
+    FBN_THUNK(fbn_bilinear_fields_bwd),
+    FBN_THUNK(fbn_bilinear_fields_bwd_supported),
+    FBN_THUNK(fbn_bilinear_fwd),
+    FBN_THUNK(fbn_bilinear_supported),
+    FBN_THUNK(fbn_bn_act_fwd),
+    FBN_THUNK(fbn_bn_act_fwd_img),
+    FBN_THUNK(fbn_bn_act_head_fwd),
+    FBN_THUNK(fbn_bn_act_head_fwd_w),
+    FBN_THUNK(fbn_bn_bwd),
+    FBN_THUNK(fbn_bn_bwd_apply),
+    FBN_THUNK(fbn_bn_bwd_chunks),
+    FBN_THUNK(fbn_bn_bwd_fused),
+    FBN_THUNK(fbn_bn_bwd_fused_img),
+    FBN_THUNK(fbn_bn_bwd_reduce),
+    FBN_THUNK(fbn_bn_eval_params),
+    FBN_THUNK(fbn_bn_finalize),
+    FBN_THUNK(fbn_bn_mean),
+    FBN_THUNK(fbn_bn_moments_finalize),
+    FBN_THUNK(fbn_bn_stats),
+    FBN_THUNK(fbn_bn_stats_pass),
+    FBN_THUNK(fbn_bn_tile_finalize),
+    FBN_THUNK(fbn_bn_tile_moments),
+    FBN_THUNK(fbn_bn_tile_stats),
+    FBN_THUNK(fbn_calib_reduce),
+    FBN_THUNK(fbn_claim_rows),
+    FBN_THUNK(fbn_clip_coef),
+    FBN_THUNK(fbn_collate),
+    FBN_THUNK(fbn_collate_f32),
+    FBN_THUNK(fbn_collate_zero_if),
+    FBN_THUNK(fbn_colsum),
+    FBN_THUNK(fbn_colsum_partial),
+    FBN_THUNK(fbn_comm_allgather),
+    FBN_THUNK(fbn_comm_allreduce),
+    FBN_THUNK(fbn_comm_alltoall),
+    FBN_THUNK(fbn_comm_alltoall_peers),
+    FBN_THUNK(fbn_comm_alltoallv),
+    FBN_THUNK(fbn_comm_heartbeat),
+    FBN_THUNK(fbn_comm_id_bytes),
+    FBN_THUNK(fbn_compact_routes),
+    FBN_THUNK(fbn_convert_bf16),
+    FBN_THUNK(fbn_copy_jobs),
+    FBN_THUNK(fbn_delong_reduce),
+    FBN_THUNK(fbn_device_ok),
+    FBN_THUNK(fbn_digest_u64),
+    FBN_THUNK(fbn_eval_pack),
+    FBN_THUNK(fbn_eval_pack_groups),
+    FBN_THUNK(fbn_eval_reduce),
+    FBN_THUNK(fbn_fields_bwd),
+    FBN_THUNK(fbn_fields_bwd_grid),
+    FBN_THUNK(fbn_fields_bwd_img),
+    FBN_THUNK(fbn_fields_bwd_partials_size),
+    FBN_THUNK(fbn_fields_bwd_slot),
+    FBN_THUNK(fbn_fields_fwd),
+    FBN_THUNK(fbn_fields_fwd_hot),
+    FBN_THUNK(fbn_gauc_reduce),
+    FBN_THUNK(fbn_gemm),
+    FBN_THUNK(fbn_gemm_bf16out),
+    FBN_THUNK(fbn_gemm_bn_bwd_part),
+    FBN_THUNK(fbn_gemm_bn_bwd_part_supported),
+    FBN_THUNK(fbn_gemm_s3),
+    FBN_THUNK(fbn_gemm_slabs),
+    FBN_THUNK(fbn_gemm_slabs_group),
+    FBN_THUNK(fbn_gemm_slabs_group_split),
+    FBN_THUNK(fbn_gemm_slabs_split),
+    FBN_THUNK(fbn_gemm_split),
+    FBN_THUNK(fbn_head_fwd),
+    FBN_THUNK(fbn_head_fwd_w),
+    FBN_THUNK(fbn_hot_rows),
+    FBN_THUNK(fbn_isotonic_apply),
+    FBN_THUNK(fbn_isotonic_fit),
+    FBN_THUNK(fbn_knn_normalize),
+    FBN_THUNK(fbn_knn_query_pool),
+    FBN_THUNK(fbn_knn_scores),
+    FBN_THUNK(fbn_owner_claim),
+    FBN_THUNK(fbn_owner_fold),
+    FBN_THUNK(fbn_owner_gather),
+    FBN_THUNK(fbn_owner_gather_self),
+    FBN_THUNK(fbn_pack_extras),
+    FBN_THUNK(fbn_pad_routes),
+    FBN_THUNK(fbn_pairs_bwd),
+    FBN_THUNK(fbn_pairs_bwd_img),
+    FBN_THUNK(fbn_pairs_fwd),
+    FBN_THUNK(fbn_pairs_fwd_img),
+    FBN_THUNK(fbn_probe_arm),
+    FBN_THUNK(fbn_probe_disarm),
+    FBN_THUNK(fbn_rank_hist),
+    FBN_THUNK(fbn_rec_fields),
+    FBN_THUNK(fbn_rec_fields_list),
+    FBN_THUNK(fbn_rec_hist_pool),
+    FBN_THUNK(fbn_rec_item_cache),
+    FBN_THUNK(fbn_rec_rank),
+    FBN_THUNK(fbn_rec_rank_list),
+    FBN_THUNK(fbn_rec_topk),
+    FBN_THUNK(fbn_rec_topk_list),
+    FBN_THUNK(fbn_ring_slot),
+    FBN_THUNK(fbn_route),
+    FBN_THUNK(fbn_route_fc),
+    FBN_THUNK(fbn_route_fc_status),
+    FBN_THUNK(fbn_row_chunks),
+    FBN_THUNK(fbn_sigmoid_bwd),
+    FBN_THUNK(fbn_sort_u64),
+    FBN_THUNK(fbn_sparse_fixup),
+    FBN_THUNK(fbn_sparse_fixup_dup),
+    FBN_THUNK(fbn_sparse_fold_fx),
+    FBN_THUNK(fbn_step_end),
+    FBN_THUNK(fbn_sum_jobs),
+    FBN_THUNK(fbn_sum_jobs2),
+    FBN_THUNK(fbn_sum_jobs_sq),
+    FBN_THUNK(fbn_sum_slices),
+    FBN_THUNK(fbn_sumsq),
+    FBN_THUNK(fbn_sumsq_flagged),
+    FBN_THUNK(fbn_sumsq_sparse),
+    FBN_THUNK(fbn_sumsq_sparse_norms),
+    FBN_THUNK(fbn_unpack_extras),
+    FBN_THUNK(fbn_unpack_sumsq),
+    FBN_THUNK(fbn_version),
+    FBN_THUNK(fbn_widen_bf16),
+};
+#undef FBN_THUNK
+
+constexpr bool thunks_sorted() {
+  for (size_t k = 1; k < sizeof(kPlanThunks) / sizeof(kPlanThunks[0]); ++k) {
+    const char *a = kPlanThunks[k - 1].name, *b = kPlanThunks[k].name;
+    while (*a && *a == *b) ++a, ++b;
+    if ((unsigned char)*a >= (unsigned char)*b) return false;
+  }
+  return true;
+}
+static_assert(thunks_sorted(), "find_thunk searches kPlanThunks by name");
 
 const PlanThunk* find_thunk(const char* name) {
   size_t lo = 0, hi = sizeof(kPlanThunks) / sizeof(kPlanThunks[0]);

@@ -687,7 +687,8 @@ extern "C" int fbn_rec_rank_list(const float* logits, int ld, int U, int C, cons
 // rec[258] the sum of the ranks >= 1, rec[259] their number: a histogram per workgroup in LDS, then
 // one integer atomic per non-empty word.  No floating point: HR / NDCG / MRR@K are host functions of
 // these integers, additive over calls.
-#define REC_RANK_WORDS 260
+#define REC_RANK_WORDS FBN_RANK_REC_WORDS
+static_assert(REC_RANK_WORDS == 1 + 256 + 3, "not ranked, ranks 1..256, above, sum, count");
 
 __global__ void __launch_bounds__(256) rank_hist_kernel(const int* rank, long long n, unsigned long long* rec) {
   __shared__ unsigned long long h[REC_RANK_WORDS];

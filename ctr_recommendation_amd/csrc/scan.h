@@ -42,10 +42,3 @@ __global__ void __launch_bounds__(256) scan_top_kernel(T* bsum, uint32_t nb) {
   }
 }
 
-// keys per workgroup of the sort's passes (include/fibinet.h publishes the same value)
-#define FBN_SORT_TILE 2048
-
-// the sort's entry points, as include/fibinet.h declares them (metrics.hip sorts its grouped keys)
-extern "C" size_t fbn_sort_u64_workspace_size(long long n);
-extern "C" int fbn_sort_u64(const uint64_t* in, long long n, int bits, void* ws, size_t ws_bytes, uint64_t* out,
-                            void* stream);

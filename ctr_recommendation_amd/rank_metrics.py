@@ -23,7 +23,7 @@ import torch
 from . import _lib
 from ._lib import call
 
-REC_WORDS = 260      # include/fibinet.h: FBN_RANK_REC_WORDS
+REC_WORDS = _lib.FBN_RANK_REC_WORDS      # 8-byte words of the record
 K_MAX = 256          # the ranks the record keeps one by one
 _NOT_RANKED, _ABOVE, _SUM, _COUNT = 0, 257, 258, 259
 

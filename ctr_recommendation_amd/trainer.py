@@ -66,9 +66,9 @@ _FC = os.environ.get("FBN_FC", "1") != "0"
 _FC_CAP = int(os.environ.get("FBN_FC_CAP", "0"))
 _FC_MARGIN = float(os.environ.get("FBN_FC_MARGIN", "1.25"))
 FC_CALIB_STEPS = 2
-FBN_GRAD_CELL = 0x20000      # include/fibinet.h: the gradient-row argument is a device cell (fbn_ring_slot)
-FBN_GRAD_BF16 = 0x40000      # include/fibinet.h: the per-entry gradient rows are bf16
-FBN_RING_BF16 = 0x40000000   # include/fibinet.h: ring_n flag, the deferred-gradient ring holds bf16 rows
+FBN_GRAD_CELL = _lib.FBN_GRAD_CELL      # the gradient-row argument is a device cell (fbn_ring_slot)
+FBN_GRAD_BF16 = _lib.FBN_GRAD_BF16      # the per-entry gradient rows are bf16
+FBN_RING_BF16 = _lib.FBN_RING_BF16      # ring_n flag, the deferred-gradient ring holds bf16 rows
 # N > 1 in bf16 mode, opt-in (FBN_RING_BF16=1): the owner's deferred-gradient ring keeps the wire's bf16
 # gradient rows as they arrive (the fold copies them instead of widening them to f32: half the ring's
 # bytes written per step and read per replayed row; the same f32 values on every read -- bitwise equal,
@@ -92,7 +92,7 @@ _CHECK_POOL = os.environ.get("FBN_CHECK_POOL", "0") == "1"
 from .schedule import OneCycle, adam_table
 
 TABLE = "item_emb.weight"
-FBN_GRAD_FULL = 0x10000      # include/fibinet.h: extra holds the full row gradient (deterministic fold)
+FBN_GRAD_FULL = _lib.FBN_GRAD_FULL      # extra holds the full row gradient (deterministic fold)
 FROZEN = ("user_emb.weight",)
 BUFFERS = ("mlp.1.running_mean", "mlp.1.running_var", "mlp.1.num_batches_tracked",
            "mlp.5.running_mean", "mlp.5.running_var", "mlp.5.num_batches_tracked")
@@ -362,7 +362,7 @@ class FiBiNETTrainer:
         seed_d = dropout_seed if dropout_seed is not None else (seed * 1000003 + 17)
         seed_d += rank * 0x9E3779B9            # independent dropout stream per rank
         self.rng = torch.tensor([seed_d & 0x7FFFFFFFFFFF, 0], dtype=torch.int64, device=dev)
-        self.sumsq = torch.zeros(64, dtype=torch.float64, device=dev)        # FBN_SUMSQ_SLOTS
+        self.sumsq = torch.zeros(_lib.FBN_SUMSQ_SLOTS, dtype=torch.float64, device=dev)
         self.sumsq_tab = torch.zeros(64, dtype=torch.float64, device=dev)
         self.coef = torch.ones(1, dtype=torch.float32, device=dev)
         self.norm = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -424,7 +424,7 @@ class FiBiNETTrainer:
             shape = (self.ring_n, self.B, 2, d) if not sharded else (self.ring_n, self.ring_cap, d)
             self.ring = self._new_ring(shape)
             self.coef_hist = torch.ones(total_steps + 1, dtype=torch.float32, device=dev)
-            self.ticket = torch.zeros(17, dtype=torch.int32, device=dev)    # fbn_adam_step_tail (FBN_TICKET_WORDS)
+            self.ticket = torch.zeros(_lib.FBN_TICKET_WORDS, dtype=torch.int32, device=dev)    # fbn_adam_step_tail
         # N > 1: forward + backward between the row exchanges replayed as hipGraph segments split at
         # the SyncBN all-reduces (_Segments), after two eager steps; FBN_SHARD_GRAPH=0 keeps it eager
         self.shard_graph = self.sharded and os.environ.get("FBN_SHARD_GRAPH", "1") != "0"

@@ -346,8 +346,6 @@ int fbn_head_fwd_w(const float* H, const float* w, const float* bias, int B, int
                    const float* labels, float* loss_terms, float* gout, float denom, const float* sample_w,
                    float pos_weight, float label_smoothing, int* err, void* stream);
 int fbn_sigmoid_bwd(const float* gp, const float* probs, float* gout, int B, void* stream);
-int fbn_outer(const float* g, const float* w, float* out, int B, int C, void* stream);
-int fbn_sum(const float* x, int n, float* out, float scale, void* stream);
 
 /* ---------------------------------------------------------------- K8 + K9 clip + Adam
  * Replaces clip_grad_norm_(10) (src/train_fibinet.py:119) and torch.optim.Adam with coupled L2

@@ -25,9 +25,10 @@ def test_constants_mirror_the_header():
     from ctr_recommendation_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "fibinet.h")).read()
     src = open(os.path.join(ROOT, "ctr_recommendation_amd", "csrc", "metrics.hip")).read()
-    for text in (hdr, src):
-        assert int(re.search(r"#define FBN_CALIB_MAX_BINS (\d+)", text).group(1)) == _lib.FBN_CALIB_MAX_BINS == 1024
-        assert int(re.search(r"#define FBN_CALIB_BIN_WORDS (\d+)", text).group(1)) == _lib.FBN_CALIB_BIN_WORDS == 8
+    assert int(re.search(r"#define FBN_CALIB_MAX_BINS (\d+)", hdr).group(1)) == _lib.FBN_CALIB_MAX_BINS == 1024
+    assert int(re.search(r"#define FBN_CALIB_BIN_WORDS (\d+)", hdr).group(1)) == _lib.FBN_CALIB_BIN_WORDS == 8
+    # the kernels take both from the header (common.h includes it): no second definition to drift
+    assert not re.search(r"#\s*define\s+FBN_CALIB_(MAX_BINS|BIN_WORDS)\b", src)
     assert _lib.SIGNATURES["fbn_calib_reduce"][1][2] is _lib.I     # bins
 
 

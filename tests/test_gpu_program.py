@@ -234,3 +234,50 @@ def test_early_wgrad_launch_bit_identical(hip_device, monkeypatch):
         res.append((losses, tr.E.clone(), tr.flat_p.clone()))
     assert res[0][0] == res[1][0]
     assert torch.equal(res[0][1], res[1][1]) and torch.equal(res[0][2], res[1][2])
+
+
+def test_program_replays_scalar_classes_the_step_never_passes(hip_device):
+    """The replay thunks come from the header's prototypes, and the training step passes only pointers,
+    int, long long and float.  Recorded here are the other scalar classes -- an unsigned long long above
+    2^63 (fbn_digest_u64's base), a size_t beside a long long (fbn_sort_u64 over 3 tiles + 5 keys) and a
+    double between integers (fbn_bn_moments_finalize, ntot = 2^25 + 1: no float holds it) -- and a replay
+    into reset outputs must give the recorded run's bits, which are checked against the host forms."""
+    from ctr_recommendation_amd import _lib, checkpoint
+    dev = hip_device
+    g = torch.Generator().manual_seed(3)
+    base = 0xFFFFFFFF00000001
+    keys = torch.randint(-(1 << 62), 1 << 62, (4096,), generator=g, dtype=torch.int64)
+    dkeys, dig = keys.to(dev), torch.zeros(1, dtype=torch.int64, device=dev)
+    n = 3 * _lib.FBN_SORT_TILE + 5
+    skeys = torch.randint(0, 1 << 62, (n,), generator=g, dtype=torch.int64)
+    sin, sout = skeys.to(dev), torch.full((n,), -1, dtype=torch.int64, device=dev)
+    ws = torch.empty(int(_lib.call("fbn_sort_u64_workspace_size", n)), dtype=torch.uint8, device=dev)
+    C, ntot, momentum, eps = 8, float((1 << 25) + 1), 0.1, 1e-5
+    mu = torch.randn(C, generator=g, dtype=torch.float64)
+    var = torch.rand(C, generator=g, dtype=torch.float64) + 0.5
+    mom = torch.cat([ntot * mu, ntot * (var + mu * mu)]).to(dev)
+    mean, invstd, run_mean = (torch.zeros(C, device=dev) for _ in range(3))
+    run_var = torch.ones(C, device=dev)
+    outs = (dig, sout, mean, invstd, run_mean, run_var)
+    init = [o.clone() for o in outs]
+    prog = _lib.StepProgram(dev)
+    with torch.cuda.device(dev), prog.recording():
+        st = _lib.stream_handle(dev)
+        _lib.call("fbn_digest_u64", dkeys.data_ptr(), 2 * len(keys), base, dig.data_ptr(), st)
+        _lib.call("fbn_sort_u64", sin.data_ptr(), n, 63, ws.data_ptr(), ws.numel(), sout.data_ptr(), st)
+        _lib.call("fbn_bn_moments_finalize", mom.data_ptr(), ntot, C, mean.data_ptr(), invstd.data_ptr(),
+                  run_mean.data_ptr(), run_var.data_ptr(), momentum, eps, 1, st)
+    torch.cuda.synchronize(dev)
+    assert prog.names == ["fbn_digest_u64", "fbn_sort_u64", "fbn_bn_moments_finalize"]
+    recorded = [o.clone() for o in outs]
+    assert dig.item() & checkpoint.MASK64 == checkpoint.digest_host(keys.numpy(), base)
+    assert torch.equal(sout.cpu(), torch.sort(skeys).values)
+    assert torch.allclose(mean.cpu().double(), mu, rtol=1e-6, atol=1e-7)
+    assert torch.allclose(invstd.cpu().double(), (var + eps).rsqrt(), rtol=1e-5)
+    assert torch.allclose(run_mean.cpu().double(), momentum * mu, rtol=1e-5, atol=1e-7)
+    for o, i in zip(outs, init):
+        o.copy_(i)
+    prog.run()
+    torch.cuda.synchronize(dev)
+    for o, r in zip(outs, recorded):
+        assert torch.equal(o, r)

@@ -14,8 +14,22 @@ def _header_symbols():
     return sorted(set(re.findall(r"\b(fbn_[a-z0-9_]+)\s*\(", src)))
 
 
+def _header_prototypes():
+    """{name: (return type, [parameter type, ...])} by this file's own reading of the header (not abi.py's):
+    a parameter's type is its words without the trailing name."""
+    src = open(os.path.join(ROOT, "include", "fibinet.h")).read()
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = re.sub(r"^\s*#.*$", " ", src, flags=re.M)
+    out = {}
+    for ret, name, params in re.findall(r"([\w \*]+?)\b(fbn_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        out[name] = (" ".join(ret.split()), [" ".join(re.sub(r"\w+\s*$", "", x).split()) for x in params])
+    return out
+
+
 def test_library_builds_loads_and_exports_header():
-    from ctr_recommendation_amd import _lib
+    import ctypes
+    from ctr_recommendation_amd import _lib, abi
     h = _lib.lib()
     assert h.fbn_version() == 1
     syms = _header_symbols()
@@ -24,6 +38,32 @@ def test_library_builds_loads_and_exports_header():
         assert hasattr(h, s), f"{s} declared in include/fibinet.h but not exported"
         assert s in _lib.SIGNATURES, f"{s} has no ctypes signature"
     assert set(_lib.SIGNATURES) == set(syms)
+    # the table is derived from the header, type by type and position by position
+    P, I, LL, D, SZ = _lib.P, _lib.I, _lib.LL, _lib.D, _lib.SZ
+    assert _lib.SIGNATURES["fbn_sort_u64"] == (I, [P, LL, I, P, SZ, P, P])
+    assert _lib.SIGNATURES["fbn_bn_moments_finalize"][1][:3] == [P, D, I]
+    assert _lib.SIGNATURES["fbn_digest_u64"][1][2] is ctypes.c_ulonglong
+    assert _lib.SIGNATURES["fbn_last_error"] == (ctypes.c_char_p, [])
+    assert _lib.SIGNATURES["fbn_probe_elapsed"] == (_lib.F, [I])
+    assert _lib.SIGNATURES["fbn_comm_load"][1] == [ctypes.c_char_p]
+    assert _lib.SIGNATURES["fbn_bn_act_fwd"][1][10] is _lib.U
+    # the parser, on literal snippets
+    snippet = "/* int fbn_no(int a); */\n#define FBN_A 7\n#define FBN_B 0x40 /* c */\n#define FBN_C (1 + 2)\n" \
+              "const char* fbn_s(void);\nsize_t fbn_q(long long n, const float *x,\n  float* const* pp, unsigned u);\n"
+    assert abi.declarations(snippet) == [("fbn_q", "size_t", ["long long", "const float*", "float* const*", "unsigned"]),
+                                         ("fbn_s", "const char*", [])]
+    assert abi.constants(snippet) == {"FBN_A": 7, "FBN_B": 64}
+    assert _lib.signatures(abi.declarations(snippet))["fbn_q"] == (SZ, [LL, P, P, _lib.U])
+    with pytest.raises(ValueError, match="fbn_u"):                 # an unnamed parameter
+        abi.declarations("int fbn_u(int, float x);")
+    with pytest.raises(ValueError, match="fbn_u"):
+        abi.declarations("int fbn_u(const float*);")
+    with pytest.raises(ValueError, match="short"):                 # a type without a ctypes mapping
+        _lib.signatures(abi.declarations("int fbn_t(short x);"))
+    with pytest.raises(ValueError, match="void"):
+        _lib.signatures(abi.declarations("void fbn_v(int x);"))
+    with pytest.raises(ValueError, match="duplicate"):
+        abi.declarations("int fbn_d(int x);\nint fbn_d(int y);")
 
 
 def test_workspace_queries_are_host_only():
@@ -136,16 +176,20 @@ def test_kernels_are_gfx950_code_objects():
     assert b"gfx950" in data
 
 
+# what a step program never replays: the program machinery itself, the communicator's setup and watchdog
+_NOT_RECORDABLE = re.compile(r"^fbn_(plan_|comm_load|comm_unique_id|comm_init|comm_destroy|comm_watch|comm_abort)")
+
+
 def test_step_program_argument_encoding():
     """Step programs record each call's arguments as 64-bit integer words and doubles and replay it
-    through a packed-argument thunk generated from include/fibinet.h (csrc/plan_thunks.inc): an
-    int -1 is the word 0xFFFF...F (the thunk casts it back to int), a float the double whose low
-    32 bits are its bits.  The committed thunks are what the header generates, every recordable
-    SIGNATURES entry has one with the same integer / floating argument counts, and the library
-    refuses a recording whose counts differ or that names no entry point."""
+    through a packed-argument thunk the compiler makes from the prototype in include/fibinet.h
+    (csrc/plan.cpp): an int -1 is the word 0xFFFF...F (the thunk casts it back to int), a float the
+    double whose low 32 bits are its bits.  The compiled table holds every recordable entry point of
+    the header with the header's integer / floating argument counts and nothing else: the library
+    refuses a recording whose counts differ or that names any other entry point."""
     import ctypes
     import struct
-    from ctr_recommendation_amd import _lib, gen_thunks
+    from ctr_recommendation_amd import _lib
     assert _lib._as_u64(None) == 0
     assert _lib._as_u64(-1) == (1 << 64) - 1
     assert _lib._as_u64(7) == 7
@@ -158,23 +202,33 @@ def test_step_program_argument_encoding():
         assert struct.unpack("<f", struct.pack("<I", bits))[0] == struct.unpack("<f", struct.pack("<f", x))[0]
     with pytest.raises(TypeError):
         _lib._as_u64(ctypes.byref(ctypes.c_int(0)))
-    hdr = open(os.path.join(ROOT, "include", "fibinet.h")).read()
-    assert open(gen_thunks.OUT).read() == gen_thunks.generate(hdr), "run python -m ctr_recommendation_amd.gen_thunks"
-    thunks = {name: args for name, args in gen_thunks.declarations(hdr)}
-    for name, (_, args) in _lib.SIGNATURES.items():
-        if name not in thunks:
-            continue
-        nf = sum(1 for a in args if a in (_lib.F, _lib.D))
-        t = thunks[name]
-        assert (len(args) - nf, nf) == (sum(1 for a in t if not (a[1] or a[2])), sum(1 for a in t if a[1] or a[2])), name
-        assert len(args) - nf <= 48 and nf <= 8, name
     h = _lib.lib()
     prog = _lib.StepProgram("cpu")
-    ia, fa = (ctypes.c_ulonglong * 4)(), (ctypes.c_double * 1)()
-    assert h.fbn_plan_add_call(ctypes.c_void_p(prog.h), b"fbn_widen_bf16", ia, 4, fa, 0) == 0     # counts match
-    assert h.fbn_plan_add_call(ctypes.c_void_p(prog.h), b"fbn_widen_bf16", ia, 3, fa, 0) != 0     # too few
-    assert h.fbn_plan_add_call(ctypes.c_void_p(prog.h), b"fbn_no_such_call", ia, 0, fa, 0) != 0
-    assert len(prog) == 1
+    ia, fa = (ctypes.c_ulonglong * 48)(), (ctypes.c_double * 8)()
+
+    def add(name, ni, nf):
+        return h.fbn_plan_add_call(ctypes.c_void_p(prog.h), name.encode(), ia, ni, fa, nf)
+    protos = _header_prototypes()
+    assert set(protos) == set(_header_symbols())
+    accepted = 0
+    for name, (ret, params) in sorted(protos.items()):
+        nf = sum(1 for t in params if t in ("float", "double"))
+        ni = len(params) - nf
+        if ret != "int" or _NOT_RECORDABLE.match(name):
+            assert add(name, ni, nf) != 0, f"{name} must not be recordable"
+            continue
+        assert ni <= 48 and nf <= 8, name
+        assert add(name, ni, nf) == 0, (name, ni, nf)
+        accepted += 1
+        if ni < 48:
+            assert add(name, ni + 1, nf) != 0, name
+        if nf < 8:
+            assert add(name, ni, nf + 1) != 0, name
+    assert accepted >= 130 and len(prog) == accepted
+    assert add("fbn_widen_bf16", 4, 0) == 0      # counts match
+    assert add("fbn_widen_bf16", 3, 0) != 0      # too few
+    assert add("fbn_no_such_call", 0, 0) != 0
+    assert len(prog) == accepted + 1
     del prog
     # an empty program runs (host only: no launches)
     prog = _lib.StepProgram("cpu")
