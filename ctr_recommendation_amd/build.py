@@ -18,7 +18,7 @@ BUILD = os.path.join(ROOT, "build", "fibinet_hip")
 LIB = os.path.join(HERE, "libfibinet_hip.so")
 HEADER = os.path.join(ROOT, "include", "fibinet.h")     # every source includes it: an edit recompiles all
 SOURCES = ["capi.cpp", "gemm.hip", "fields.hip", "mlp.hip", "optim.hip", "exchange.hip", "collate.hip", "bilinear.hip", "metrics.hip",
-           "sort.hip", "isotonic.hip", "recommend.hip", "retrieve.hip", "digest.hip", "plan.cpp", "comm.cpp"]
+           "sort.hip", "isotonic.hip", "recommend.hip", "retrieve.hip", "diversify.hip", "digest.hip", "plan.cpp", "comm.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wno-unused-result",

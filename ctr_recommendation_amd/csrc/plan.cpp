@@ -185,6 +185,8 @@ constexpr PlanThunk kPlanThunks[] = {
     FBN_THUNK(fbn_knn_normalize),
     FBN_THUNK(fbn_knn_query_pool),
     FBN_THUNK(fbn_knn_scores),
+    FBN_THUNK(fbn_list_ild),
+    FBN_THUNK(fbn_mmr_select),
     FBN_THUNK(fbn_owner_claim),
     FBN_THUNK(fbn_owner_fold),
     FBN_THUNK(fbn_owner_gather),

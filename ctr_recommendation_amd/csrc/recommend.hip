@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "fields_common.h"
+#include "rec_key.h"
 
 static bool rec_dim_ok(int D) { return D == 16 || D == 32 || D == 64 || D == 128 || D == 256; }
 
@@ -324,7 +325,7 @@ extern "C" int fbn_rec_fields_list(const int64_t* item_id, const int64_t* likes,
 // key = {ordered image of the f32 logit (32) | 0xFFFFFFFF - catalogue position (32)}: unique per
 // candidate, and a larger key is a larger logit or, on equal logits, a smaller position.  0 is the
 // "no candidate" key (excluded, filtered out, or an empty slot); a NaN logit takes the high word 1,
-// below -inf's 0x007FFFFF.
+// below -inf's 0x007FFFFF (rec_key.h).
 #define REC_TILE 256     // keys a workgroup takes in per round
 #define REC_SEG 1024     // candidates per workgroup of the selection launch
 #define REC_KMAX 256
@@ -344,18 +345,6 @@ struct RecTopkArgs {
   int64_t* out_slot;
   int ldp, M;
 };
-
-__device__ __forceinline__ unsigned long long rec_key(float x, unsigned pos, bool& nan) {
-  const unsigned b = __float_as_uint(x);
-  nan = (b & 0x7FFFFFFFu) > 0x7F800000u;
-  const unsigned o = nan ? 1u : ((b & 0x80000000u) ? ~b : (b | 0x80000000u));
-  return ((unsigned long long)o << 32) | (unsigned long long)(0xFFFFFFFFu - pos);
-}
-__device__ __forceinline__ float rec_key_logit(unsigned long long key) {
-  const unsigned o = (unsigned)(key >> 32);
-  if (o == 1u) return __uint_as_float(0x7FC00000u);
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
-}
 
 // One workgroup keeps the K largest of a key stream: buf[0, 256) is the running list (descending,
 // zeros past the keys seen), buf[256, 512) takes a tile of 256 new keys -- those that cannot enter
@@ -395,10 +384,7 @@ __global__ void __launch_bounds__(256) rec_topk_kernel(RecTopkArgs p) {
           key = rec_key(p.logits[(size_t)u * p.Mc + j], (unsigned)col, nan);
           if (nan) atomicOr(p.status, 1u);
           if (p.exclude) {
-            const long long id = p.item_id[m];
-            bool ex = id == 0;
-            for (int l = 0; l < L; ++l) ex |= hist[l] != 0 && hist[l] == id;
-            if (ex) key = 0ull;
+            if (rec_id_excluded(hist, L, p.item_id[m])) key = 0ull;
           }
         }
       } else {

@@ -27,6 +27,11 @@ front of those lists (csrc/retrieve.hip): cosine similarity between L2-normalise
 into the same ``fbn_rec_topk`` / ``fbn_rec_rank``; a user's query is the normalised sum of its history
 items' vectors, which ranks as the mean cosine to them does.
 
+``diversify`` / ``list_diversity`` / ``evaluate_diversity`` (csrc/diversify.hip) re-rank a
+user's list by greedy maximal marginal relevance -- relevance against the largest cosine to what is
+already picked, in one of the retrieval spaces -- and measure the intra-list diversity of finished lists;
+``recommend(lam=...)`` puts the re-ranking behind the retrieval stage.
+
 Single device, bilinear "all"; a row-sharded table is out of scope.
 """
 from __future__ import annotations
@@ -45,6 +50,7 @@ CATALOGUE_KEYS = ("item_id", "likes_level", "views_level", "item_emb_d128")
 SPACES = ("content", "mm", "id")            # retrieval vector spaces
 DEFAULT_KNN_CHUNK_BYTES = 64 << 20
 Q_MAX = 65535                               # include/fibinet.h: fbn_knn_scores / fbn_rec_topk
+MMR_MAX_C = _lib.FBN_MMR_MAX_C              # include/fibinet.h: fbn_mmr_select's list length
 
 
 def _state_of(state) -> Dict[str, torch.Tensor]:
@@ -104,6 +110,44 @@ def _check_knn(space: str, n: Optional[int] = None, *, what: str = "n", by: Opti
     if not 1 <= int(item_seq.shape[0]) <= Q_MAX:
         raise ValueError(f"item_seq holds {int(item_seq.shape[0])} users: need 1..{Q_MAX} per call")
     return int(item_seq.shape[0])
+
+
+def _check_lam(lam) -> float:
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:                  # NaN fails both comparisons
+        raise ValueError(f"lam must be a number in [0, 1], not {lam!r}")
+    return lam
+
+
+def _check_diversify(item_seq, candidates, k, lam, space: str, relevance, by: str):
+    """The argument checks of ``diversify``, before anything is launched: -> (U, C, lam).  Shapes only,
+    so it needs no device."""
+    if space not in SPACES:
+        raise ValueError(f"space must be one of {SPACES}, not {space!r}")
+    lam = _check_lam(lam)
+    U, C = _check_lists(item_seq, candidates, by, k=k)
+    if C > MMR_MAX_C:
+        raise ValueError(f"candidates holds {C} slots per user: diversify takes at most {MMR_MAX_C}")
+    if U > Q_MAX:
+        raise ValueError(f"candidates holds {U} users: need 1..{Q_MAX} per call")
+    if isinstance(relevance, torch.Tensor):
+        if relevance.dtype != torch.float32 or tuple(relevance.shape) != (U, C):
+            raise ValueError(f"relevance must be 'prob', 'logit' or a float32 tensor [{U}, {C}]")
+    elif relevance not in ("prob", "logit"):
+        raise ValueError(f"relevance must be 'prob', 'logit' or a float32 tensor [U, C], not {relevance!r}")
+    return U, C, lam
+
+
+def _check_positions(index, space: str):
+    """The argument checks of ``list_diversity``: -> (U, K)."""
+    if space not in SPACES:
+        raise ValueError(f"space must be one of {SPACES}, not {space!r}")
+    if not isinstance(index, torch.Tensor) or index.dim() != 2 or index.is_floating_point():
+        raise ValueError("index must be an integer tensor [U, K] of catalogue positions")
+    U, K = int(index.shape[0]), int(index.shape[1])
+    if not 1 <= U <= Q_MAX or not 1 <= K <= K_MAX:
+        raise ValueError(f"index is {tuple(index.shape)}: need 1..{Q_MAX} lists of 1..{K_MAX} positions")
+    return U, K
 
 
 def _knn_chunks(M: int, Q: int, chunk_bytes: int):
@@ -686,14 +730,21 @@ class Recommender:
 
     @torch.no_grad()
     def recommend(self, item_seq: torch.Tensor, k: int, *, n_candidates: int = 200, space: str = "content",
-                  exclude_history: bool = True) -> Dict[str, torch.Tensor]:
+                  exclude_history: bool = True, lam: Optional[float] = None) -> Dict[str, torch.Tensor]:
         """Two stages: :meth:`retrieve` ``n_candidates`` per user, then :meth:`topk_lists` over them
         (``by="index"``).  Returns ``topk_lists``' dict; its logits are the eval forward's for those
-        pairs, exactly as ``topk`` gives them.  A user without a usable history gets an all -1 row."""
+        pairs, exactly as ``topk`` gives them.  A user without a usable history gets an all -1 row.
+        ``lam`` (a number in [0, 1]): the second stage is :meth:`diversify` over the shortlist instead,
+        in the same ``space`` and with its defaults, and its dict is returned."""
         _check_knn(space, n_candidates, what="n_candidates", item_seq=item_seq)
         if not 1 <= int(k) <= K_MAX:
             raise ValueError(f"k must be in 1..{K_MAX}")
+        if lam is not None:
+            lam = _check_lam(lam)
         cands = self.retrieve(item_seq, n_candidates, space=space, exclude_history=exclude_history)["index"]
+        if lam is not None:
+            return self.diversify(item_seq, cands, k, lam=lam, space=space, by="index",
+                                  exclude_history=exclude_history)
         return self.topk_lists(item_seq, cands, k, exclude_history=exclude_history, by="index")
 
     @torch.no_grad()
@@ -747,5 +798,137 @@ class Recommender:
                          L, int(bool(exclude_history)), ptr(tpos), ptr(rank), ptr(n_el), ptr(self.status), st)
                     metrics.update(rank)
         result = metrics.compute(ns)
+        self.check_ids()
+        return result
+
+    # ------------------------------------------------------------------ diversity
+    def _seq(self, item_seq: Optional[torch.Tensor]):
+        """(seq [U, L] on the device or None, L) as :meth:`_hist` keeps it, without pooling anything."""
+        if item_seq is None:
+            return None, 0
+        seq = item_seq.to(self.device).long()
+        if seq.shape[1] > self.max_len:
+            seq = seq[:, seq.shape[1] - self.max_len:]         # the collator keeps the last max_len
+        L = int(seq.shape[1])
+        return (seq.contiguous(), L) if L else (None, 0)
+
+    def _mmr(self, rel, pos, seq, L, k, lam, xn, exclude_history, st) -> Dict[str, torch.Tensor]:
+        """One ``fbn_mmr_select`` call over rel [U, C] f32 and pos [U, C] catalogue positions."""
+        dev, (U, C) = self.device, pos.shape
+        out = {n: torch.empty((U, k), dtype=torch.int64, device=dev) for n in ("slot", "index", "item_id")}
+        out.update({n: torch.empty((U, k), dtype=torch.float32, device=dev) for n in ("relevance", "mmr", "penalty")})
+        call("fbn_mmr_select", ptr(rel), int(rel.stride(0)), ptr(pos), C, U, C, ptr(xn), self.M, int(xn.shape[1]),
+             ptr(self.cat["item_id"]), ptr(seq), L, int(bool(exclude_history)), lam, k, ptr(out["slot"]),
+             ptr(out["index"]), ptr(out["item_id"]), ptr(out["relevance"]), ptr(out["mmr"]), ptr(out["penalty"]),
+             ptr(self.status), st)
+        return out
+
+    @torch.no_grad()
+    def diversify(self, item_seq: Optional[torch.Tensor], candidates: torch.Tensor, k: int, *, lam: float = 0.7,
+                  space: str = "content", relevance="prob", by: str = "item_id",
+                  exclude_history: bool = True) -> Dict[str, torch.Tensor]:
+        """Greedy maximal-marginal-relevance re-ranking of each user's own list (``fbn_mmr_select``,
+        DESIGN.md §27): k picks, each the eligible unpicked slot with the largest
+        ``lam * relevance - (1 - lam) * max cosine to the slots picked so far`` in ``space``; equal scores
+        go to the smaller slot.  ``candidates`` [U, C <= 1024], ``by``, empty slots and ``exclude_history``
+        are :meth:`topk_lists`'.  ``relevance``: ``"prob"`` or ``"logit"`` -- the eval forward's numbers
+        for the listed pairs, through :meth:`score_lists`' sweep -- or a float32 tensor [U, C] of the
+        caller's own scores, in which case nothing is scored.  Returns ``slot``, ``index``, ``item_id``,
+        ``relevance``, ``mmr`` (the score when picked) and ``penalty`` (that maximum cosine, 0 for the
+        first pick), all [U, k], best first; with fewer than k eligible slots the tail is -1, -1, -1,
+        -inf, -inf, 0.  ``lam=1`` is :meth:`topk_lists`' order on the same relevance.  A NaN relevance
+        ranks last and sets bit 0 of ``status``.  ``item_seq=None`` with one row is the cold user.
+        Nothing is copied to the host and nothing synchronises."""
+        U, C, lam = _check_diversify(item_seq, candidates, k, lam, space, relevance, by)
+        k, dev = int(k), self.device
+        with torch.cuda.device(dev):
+            st = _lib.stream_handle(dev)
+            pos = self._lists(candidates, by)
+            if isinstance(relevance, torch.Tensor):
+                seq, L = self._seq(item_seq)
+                rel = relevance.to(dev)
+                if rel.stride(1) != 1:
+                    rel = rel.contiguous()
+            else:
+                seq, hist, U, L = self._hist(item_seq, st)
+                rel = self._sweep(hist, U, relevance == "logit", pos)
+            return self._mmr(rel, pos, seq, L, k, lam, self._space(space, st), exclude_history, st)
+
+    @torch.no_grad()
+    def list_diversity(self, index: torch.Tensor, *, space: str = "content") -> Dict[str, torch.Tensor]:
+        """Intra-list diversity of finished lists: ``index`` [U, K <= 256] holds catalogue positions, -1
+        (or anything outside the catalogue) an empty slot.  Returns ``{"ild": float64 [U], "n_pairs":
+        int32 [U]}``: the mean of ``1 - cosine`` in ``space`` over the pairs of a list's entries, 0 for a
+        list with fewer than two.  No host copy and no sync; two calls give equal bits."""
+        U, K = _check_positions(index, space)
+        dev = self.device
+        with torch.cuda.device(dev):
+            st = _lib.stream_handle(dev)
+            xn = self._space(space, st)
+            pos = index.to(dev).long().contiguous()
+            out = {"ild": torch.empty(U, dtype=torch.float64, device=dev),
+                   "n_pairs": torch.empty(U, dtype=torch.int32, device=dev)}
+            call("fbn_list_ild", ptr(pos), K, U, K, ptr(xn), self.M, int(xn.shape[1]), ptr(out["ild"]),
+                 ptr(out["n_pairs"]), st)
+        return out
+
+    @torch.no_grad()
+    def evaluate_diversity(self, pairs, k: int = 10, lams=(1.0, 0.7, 0.5), *, n_candidates: int = 200,
+                           space: str = "content", exclude_history: bool = True, max_users: Optional[int] = None,
+                           users_per_block: int = 64) -> Dict:
+        """What a value of lam costs and buys on held-out interactions.  ``pairs`` and the selection of
+        the positive rows are :meth:`evaluate`'s.  Every block of users is retrieved once
+        (``n_candidates`` in ``space``) and scored once (probabilities); for each lam the shortlist goes
+        through :meth:`diversify` and :meth:`list_diversity`.  Returns ``{lam: {"hr": {k: share of the
+        users whose held-out item id is in their list}, "ild": mean ILD over the users whose list has
+        two entries or more, "n_ild": their number, "n": the number of users}}``.  The sums stay on the
+        device and are read once at the end; selecting a batch's positive rows synchronises once per
+        batch.  Ends with ``check_ids()``."""
+        if not 1 <= int(k) <= K_MAX:
+            raise ValueError(f"k must be in 1..{K_MAX}")
+        lams = [_check_lam(x) for x in lams]
+        if not lams:
+            raise ValueError("lams is empty")
+        if space not in SPACES:
+            raise ValueError(f"space must be one of {SPACES}, not {space!r}")
+        if not 1 <= int(n_candidates) <= K_MAX:
+            raise ValueError(f"n_candidates must be in 1..{K_MAX}")
+        upb, k = int(users_per_block), int(k)
+        if not 1 <= upb <= Q_MAX:
+            raise ValueError(f"users_per_block must be in 1..{Q_MAX}")
+        left = None if max_users is None else int(max_users)
+        dev = self.device
+        hits = torch.zeros(len(lams), dtype=torch.int64, device=dev)
+        n_ild = torch.zeros(len(lams), dtype=torch.int64, device=dev)
+        s_ild = torch.zeros(len(lams), dtype=torch.float64, device=dev)
+        n = 0
+        for batch, labels in pairs:
+            if left is not None and left <= 0:
+                break
+            rows = (labels.to(dev).reshape(-1) == 1).nonzero().reshape(-1)      # the per-batch sync
+            if left is not None:
+                rows = rows[:left]
+                left -= int(rows.numel())
+            if rows.numel() == 0:
+                continue
+            n += int(rows.numel())
+            seqs, tgts = batch["item_seq"].to(dev)[rows], batch["item_id"].to(dev).reshape(-1)[rows].long()
+            for r0 in range(0, int(rows.numel()), upb):
+                seq, tgt = seqs[r0:r0 + upb], tgts[r0:r0 + upb]
+                cands = self.retrieve(seq, n_candidates, space=space, exclude_history=exclude_history)["index"]
+                rel = self.score_lists(seq, cands, by="index")
+                for i, lam in enumerate(lams):
+                    out = self.diversify(seq, cands, k, lam=lam, space=space, relevance=rel, by="index",
+                                         exclude_history=exclude_history)
+                    hits[i] += ((out["item_id"] == tgt[:, None]) & (out["index"] >= 0)).any(dim=1).sum()
+                    d = self.list_diversity(out["index"], space=space)
+                    some = d["n_pairs"] > 0
+                    n_ild[i] += some.sum()
+                    s_ild[i] += torch.where(some, d["ild"], torch.zeros_like(d["ild"])).sum()
+        got = torch.stack([hits.double(), n_ild.double(), s_ild]).cpu()          # the one read
+        result = {}
+        for i, lam in enumerate(lams):
+            h, c, s = int(got[0, i]), int(got[1, i]), float(got[2, i])
+            result[lam] = {"hr": {k: h / n if n else 0.0}, "ild": s / c if c else 0.0, "n_ild": c, "n": n}
         self.check_ids()
         return result

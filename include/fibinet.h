@@ -1025,6 +1025,43 @@ int fbn_knn_query_pool(const int64_t* item_seq, int U, int L, const int* pos_of_
 int fbn_knn_scores(const float* Qn, int ldq, const int64_t* q_pos, const float* Xn, int M, int Q, int m0, int Mc,
                    int D, float* S, void* stream);
 
+/* ---------------------------------------------------------------- serving: diversity (MMR re-ranking, ILD)
+ * The reference returns scores (src/Prediction.py:106-113) and has no re-ranking of its own.  Both entry
+ * points read the L2-normalised matrix Xn [M][D] of fbn_knn_normalize, D in {16,32,64,128,256}, and
+ * sim(a, b) is the f32 dot of two of its rows as ONE fmaf chain in ascending k from a +0 accumulator:
+ * the bits fbn_knn_scores gives for the pair.
+ *
+ * fbn_mmr_select: greedy maximal marginal relevance over each user's own list; replaces a host loop of
+ * K arg-maxes over a U x C x C similarity tensor.  Slot j of user u has relevance rel[u * ldr + j] and
+ * catalogue position m = cand_pos[u * ldp + j]; it is live iff 0 <= m < M and, with exclude != 0, it
+ * passes fbn_rec_topk_list's id rule (item_id[m] != 0 and no non-padding id of item_seq[u] ([U][L]) equals
+ * it).  A position listed in two slots is two candidates.  With S_t the slots picked before step t and
+ * oml = 1.0f - lam in f32:
+ *   pen_t(j) = max_{s in S_t} sim(j, s)                         (t >= 1; the raw maximum, not clamped at 0)
+ *   mmr_0(j) = lam * rel_j          mmr_t(j) = fmaf(lam, rel_j, -(oml * pen_t(j)))          each + 0.0f
+ *   pick_t   = the live unpicked slot with the largest key {ordered(mmr_t(j)), 0xFFFFFFFF - j}
+ * -- fbn_rec_topk's order-preserving image, so equal scores (-0.0 and +0.0 too) go to the smaller slot
+ * and a NaN ranks below every number.  A NaN rel in a live slot sets bit 0 of *status; in a slot that is
+ * not live it sets nothing.  Outputs [U][K], best first: out_slot, out_index (catalogue position),
+ * out_item (id), out_rel (as given), out_mmr (the score when picked), out_pen (pen_t; 0 at t = 0); with
+ * fewer than K live slots the tail is -1, -1, -1, -inf, -inf, 0.  One workgroup per user: a user's
+ * result depends on its own row only, not on U or the other users.  1 <= K <= 256, 0 <= C <=
+ * FBN_MMR_MAX_C, 0 <= L <= 32, lam finite in [0, 1], ldr >= C, ldp >= C, 0 <= U <= 65535, M >= 0 (else
+ * FBN_ERR_ARG, checked on the host before any device work); U == 0 or C == 0 launches nothing. */
+#define FBN_MMR_MAX_C 1024
+int fbn_mmr_select(const float* rel, int ldr, const int64_t* cand_pos, int ldp, int U, int C, const float* Xn, int M,
+                   int D, const int64_t* item_id, const int64_t* item_seq, int L, int exclude, float lam, int K,
+                   int64_t* out_slot, int64_t* out_index, int64_t* out_item, float* out_rel, float* out_mmr,
+                   float* out_pen, unsigned* status, void* stream);
+/* fbn_list_ild: intra-list diversity of finished lists list_pos [U][ldp] of catalogue positions.  Over the
+ * n live entries (0 <= m < M) of list_pos[u][0, K): n_pairs[u] = n (n - 1) / 2 and ild[u] = sum_{a < b}
+ * (1.0 - (double) sim(a, b)) / n_pairs[u], 0 when n < 2; a position listed twice is two entries.  The f64
+ * terms are added in an order fixed by (a, b) -- per entry a over ascending b, then over ascending a --
+ * with no atomics: two calls give equal bits.  1 <= K <= 256, ldp >= K, 0 <= U <= 65535, M >= 0 (else
+ * FBN_ERR_ARG on the host); U == 0 launches nothing. */
+int fbn_list_ild(const int64_t* list_pos, int ldp, int U, int K, const float* Xn, int M, int D, double* ild,
+                 int* n_pairs, void* stream);
+
 /* ---------------------------------------------------------------- step programs (native step driver)
  * Replaces the Python loop body that issues one training step (src/train_fibinet.py:113-123): the
  * host records a step's calls of this library -- entry point, arguments, and the cross-stream

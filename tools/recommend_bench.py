@@ -35,6 +35,12 @@ L = 20, K = 10), same method:
 and fbn_knn_scores alone at Q = 64 and Q = 8192 over the whole catalogue beside fbn_gemm (fp32, transB)
 on the same normalised operands (back-to-back calls per timed run, the two interleaved), with the largest
 difference between their outputs.  Written to profiles/retrieve_two_stage.json.
+
+--diversify: MMR re-ranking behind the retrieval stage, same shape and method:
+  (a) recommend_ms      Recommender.recommend(k = 10, n_candidates = 200): retrieve + topk_lists
+  (b) recommend_lam_ms  Recommender.recommend(..., lam = 0.7): retrieve + diversify
+and, from separate probed runs of (b), the kernel span of fbn_mmr_select.  Written to
+profiles/diversify.json.
 """
 import argparse
 import json
@@ -311,6 +317,77 @@ def retrieve_bench(args, rec, seq):
     print(json.dumps(res))
 
 
+def diversify_bench(args, rec, seq):
+    """--diversify: recommend(lam=None) beside recommend(lam=args.lam), then fbn_mmr_select's kernel span."""
+    import ctr_recommendation_amd.recommend as rmod
+    dev, U, K = rec.device, seq.shape[0], args.k
+    n_cand, space, lam = args.candidates, "content", args.lam
+
+    def plain():
+        return rec.recommend(seq, K, n_candidates=n_cand, space=space)
+
+    def diverse():
+        return rec.recommend(seq, K, n_candidates=n_cand, space=space, lam=lam)
+
+    plain(), diverse()                                      # warm-up (allocations, bf16 images, the space)
+    ta, tb = [], []
+    for _ in range(args.runs):                              # interleaved A/B
+        t, ra = _timed(plain)
+        ta.append(t)
+        t, rb = _timed(diverse)
+        tb.append(t)
+    rec.check_ids()
+    # what the re-ranking did to these lists (random weights and vectors: a property of this synthetic
+    # input, not of any model)
+    ild = {n: rec.list_diversity(r["index"], space=space) for n, r in (("plain", ra), ("diverse", rb))}
+    ild = {n: round(float(v["ild"][v["n_pairs"] > 0].mean().item()), 6) for n, v in ild.items()}
+    overlap = sum(len(set(ra["index"][u].tolist()) & set(rb["index"][u].tolist())) for u in range(U)) / (U * K)
+
+    # a separate probed run of the diversified route: kernel spans per stage
+    stages = {}
+    call0 = rmod.call
+
+    def probed_call(name, *a):
+        if name.startswith("fbn_knn_") or name in ("fbn_rec_topk", "fbn_mmr_select", "fbn_rec_hist_pool"):
+            kp = _lib.KernelProbe()
+            stages.setdefault(name, []).append((kp, None))
+            try:
+                return call0(name, *a)
+            finally:
+                kp.done()
+        return call0(name, *a)
+
+    rmod.call = probed_call
+    spans = []
+    for _ in range(args.runs):
+        stages.clear()
+        diverse()
+        torch.cuda.synchronize()
+        spans.append(_span(stages["fbn_mmr_select"]))
+    rmod.call = call0
+    stage_ms = {k[4:]: round(_span(v), 4) for k, v in stages.items()}
+
+    ma, mb = statistics.median(ta), statistics.median(tb)
+    D = int(rec._knn[space].shape[1])
+    res = {"device": torch.cuda.get_device_name(dev), "users": U, "items": rec.M, "k": K, "d": rec.d,
+           "dtype": args.dtype, "space": space, "space_dim": D, "n_candidates": n_cand, "lam": lam, "runs": args.runs,
+           "statistic": "median of runs (HIP events, one process, the two routes interleaved)",
+           "recommend_ms": round(ma, 4), "recommend_lam_ms": round(mb, 4), "added_ms": round(mb - ma, 4),
+           "ratio_lam_over_plain": round(mb / ma, 3),
+           "recommend_ms_min_max": [round(min(ta), 4), round(max(ta), 4)],
+           "recommend_lam_ms_min_max": [round(min(tb), 4), round(max(tb), 4)],
+           "raw_recommend_ms": [round(t, 4) for t in ta], "raw_recommend_lam_ms": [round(t, 4) for t in tb],
+           "mmr_select_kernel_ms": round(statistics.median(spans), 4),
+           "mmr_select_kernel_ms_min_max": [round(min(spans), 4), round(max(spans), 4)],
+           "lam_route_stage_kernel_ms": stage_ms,
+           "mean_ild_on_random_input": ild, "list_overlap_on_random_input": round(overlap, 4)}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--users", type=int, default=64)
@@ -326,11 +403,14 @@ def main():
     ap.add_argument("--slots", type=int, default=500, help="--lists: slots per user")
     ap.add_argument("--list-calls", type=int, default=20, help="--lists: topk_lists calls per timed run")
     ap.add_argument("--retrieve", action="store_true", help="time recommend (retrieve + topk_lists) against topk")
-    ap.add_argument("--candidates", type=int, default=200, help="--retrieve: shortlist length per user")
+    ap.add_argument("--candidates", type=int, default=200, help="--retrieve / --diversify: shortlist length per user")
+    ap.add_argument("--diversify", action="store_true", help="time recommend(lam) against recommend(lam=None)")
+    ap.add_argument("--lam", type=float, default=0.7, help="--diversify: the MMR trade-off")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join("profiles", "recommend_lists.json" if args.lists else
+                                "diversify.json" if args.diversify else
                                 "retrieve_two_stage.json" if args.retrieve else
                                 "recommend_rank_eval.json" if args.rank_eval else "recommend_vs_expanded.json")
     if args.lists:
@@ -350,6 +430,8 @@ def main():
     rec = Recommender(model.state_dict(), cfg, cat, device=dev, chunk_rows=args.chunk_rows)
     if args.retrieve:
         return retrieve_bench(args, rec, seq)
+    if args.diversify:
+        return diversify_bench(args, rec, seq)
     if args.rank_eval:
         return rank_eval(args, rec, seq, torch.randint(0, M, (U,), generator=g).to(dev))
     catd = {k: v.to(dev) for k, v in rec.cat.items()}
